@@ -3,7 +3,13 @@
 bench.py -- headline benchmark of the BabyJubJub hot path on MI355X.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload fixed_base|var_base|verify|poseidon5|...]
-                  [--batch B] [--window-bits W] [--no-cpu-baseline] [--no-also] [--no-strong] [--native-multi]
+                  [--batch B] [--window-bits W] [--dump-outputs DIR]
+                  [--full [--no-cpu-baseline] [--no-also] [--no-strong]] [--native-multi]
+
+A plain run measures the headline only: it sets up, warms up (W launches, then --warmup-seconds), times the K steps under the
+protocol that makes `value`, writes the outputs of the last timed step when --dump-outputs is given, and prints the line.
+`--full` measures everything described below as well (the one-stream control, per-launch and Infinity-Cache passes, the oracle
+sample comparison, cpu_baseline, roofline / valu, clock telemetry, `also`, `strong`).
 
 A "step" is one pass of the hot path over one batch of synthetic input that is already resident in HBM (SplitMix64
 streams of SURVEY.md 8d; the timed loop rotates over 4 distinct resident batches).  Default workload = BASELINE.json
@@ -18,13 +24,14 @@ scaling) -- and `value` is the whole-job rate: N * batch * K / max-over-ranks ti
 OUTPUT.  stdout gets exactly ONE line, printed last: the compact record of babyjubjub-rs_amd/benchline.py (<= 4 KB: the
 contract's keys, `roofline`, `cpu_baseline`, every other workload as {value, unit, ms_per_step, roofline_frac, valu_frac,
 kernel}).  Everything measured -- per-launch event statistics, clock blocks, notes -- goes to bench_detail.json
-(`--detail-out`) and to stderr as one `bench_detail: {...}` line.  The detail record carries
+(`--detail-out`) and to stderr as one `bench_detail: {...}` line.  With --full the detail record carries
   also    : the EdDSA-verify and variable-base halves of BASELINE's metric (1 M per GPU), with their own roofline /
             cpu_baseline blocks (1-GPU run) -- same steps / warm-up protocol
   strong  : fixed total work split over the N ranks: 2^20 fixed-base mults, and BASELINE configs[4] = 2^24 verifies,
             pre-sharded and in cfg 5's literal shape (rank 0 holds everything; RCCL scatter -> kernels -> gather)
   roofline / cpu_baseline / valu : see DESIGN.md section 6
-The process exits non-zero when any oracle sample comparison fails (a miscomputing build must not publish a number).
+With --full the process exits non-zero when any oracle sample comparison fails (a miscomputing build must not publish a number);
+a plain run compares nothing (`parity_sample_ok` is null): --dump-outputs lets two builds be compared output for output.
 `--native-multi` instead drives all N GPUs from ONE process through the C ABI's bjj_multi_* entry points
 (ncclCommInitAll + grouped ncclScatter / ncclGather inside libbjj_hip.so).
 """
@@ -79,6 +86,16 @@ KERNEL = {"fixed_base": "bjj_k_mul_fixed_base", "var_base": "bjj_k_mul_var_base_
 # (per-launch HIP events; what the rocprofv3 summaries under profiles/ profile), and `single_stream` carries its rate.
 DEFAULT_STREAMS = {"fixed_base": 2, "verify": 2, "var_base": 2, "verify_compressed": 2, "fixed_base_compressed": 2}
 HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md: 8.0 TB/s spec
+# --dump-outputs: the arrays a caller of the timed path receives, (name, Batch attribute, bytes per item); written as float32,
+# one value per byte (exact), at most DUMP_BYTES in all -- beyond that a sample of rows drawn with DUMP_SEED
+OUTPUTS = {"fixed_base": (("points", "d_out", 64),), "fixed_base_compressed": (("points_compressed", "d_out", 32),),
+           "var_base": (("points", "d_out", 64),), "poseidon5": (("hashes", "d_out", 32),),
+           "sign": (("r8", "d_out", 64), ("s", "d_s", 32), ("ok", "d_ok", 1)),
+           "point_add": (("points", "d_out", 64),), "compress": (("points_compressed", "d_out", 32),),
+           "decompress": (("points", "d_out", 64), ("ok", "d_ok", 1)),
+           "verify": (("verdicts", "d_out", 1),), "verify_compressed": (("verdicts", "d_out", 1),)}
+DUMP_BYTES = 32 << 20
+DUMP_SEED = 20240611
 T8 = (4342719913949491028786768530115087822524712248835451589697801404893164183326,
       4826523245007015323400664741523384119579596407052839571721035538011798951543)  # a point of order 8 (SURVEY.md 8d cfg 3)
 
@@ -218,9 +235,17 @@ def parse():
     ap.add_argument("--signer-constant-time", action="store_true",
                     help="bjj_set_signer_constant_time(ctx, 1): the signer workloads (sign) scan the small 4-bit table instead of "
                          "indexing the fixed-base table with secret digits")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-also", action="store_true", help="skip the secondary workload lines")
-    ap.add_argument("--no-strong", action="store_true", help="skip the fixed-total-work (strong scaling / cfg 5) lines")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline as well: the one-stream control, the per-launch and Infinity-Cache "
+                         "passes, the oracle sample comparison, cpu_baseline, roofline / valu, clock telemetry, `also` and `strong` "
+                         "(a plain run sets up, warms up, times the K steps and prints the line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step computed to DIR/<name>.npy, float32, one value per "
+                         "byte of the library's output records (rank 0's block; a fixed seeded sample of rows when all of them would "
+                         "exceed %d MiB)" % (DUMP_BYTES >> 20))
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-also", action="store_true", help="--full: skip the secondary workload lines")
+    ap.add_argument("--no-strong", action="store_true", help="--full: skip the fixed-total-work (strong scaling / cfg 5) lines")
     ap.add_argument("--native-multi", action="store_true",
                     help="ONE process, all --gpus devices through bjj_multi_* (RCCL inside the library)")
     ap.add_argument("--transport", default="rccl", choices=["rccl", "peer"],
@@ -460,6 +485,23 @@ class Workload:
         if k == "verify_compressed":
             return bool((got[~B.bad] == 1).all()) and bool((got[B.bad] != 1).all()) and bool((got[idx] == want).all())
         return bool((got == (~B.bad).astype(np.uint8)).all()) and bool((got[idx] == want).all())
+
+    def dump(self, k, out_dir):
+        """--dump-outputs: the outputs launch k wrote (its batch's output buffers) to out_dir/<name>.npy as float32, one value per
+        byte, shape (rows, bytes per item) or (rows,) for one byte per item.  Every row when they fit in DUMP_BYTES, else the same
+        DUMP_SEED sample of rows (sorted) for every output.  Returns {name: shape}."""
+        n, specs = self.n, OUTPUTS[self.kind]
+        B = self.batches[k % len(self.batches)]
+        m = min(n, DUMP_BYTES // (4 * sum(w for _, _, w in specs)))
+        idx = slice(None) if m == n else np.sort(np.random.default_rng(DUMP_SEED).choice(n, m, replace=False))
+        os.makedirs(out_dir, exist_ok=True)
+        shapes = {}
+        for name, attr, width in specs:
+            a = self.rows(attr, width, idx, B).astype(np.float32)
+            a = a.reshape(-1) if width == 1 else a
+            np.save(os.path.join(out_dir, name + ".npy"), a)
+            shapes[name] = list(a.shape)
+        return shapes
 
 
 def timed_steps(wl, steps, warmup, world, warm_s=0.0, streams=None):
@@ -834,11 +876,22 @@ def step_stats(step_ms, n, world):
             "p90_ms": float(np.percentile(a, 90)), "value_from_median": world * n / (med * 1e-3)}
 
 
-def measure(ctx, kind, n, offset, dev, stream, steps, warmup, warm_s, world, nb, orc, with_cpu, rank, stream2=None):
+def measure(ctx, kind, n, offset, dev, stream, steps, warmup, warm_s, world, nb, orc, with_cpu, rank, stream2=None, full=True):
     """one full measurement block of a workload on this rank: (wl, dt over the K timed steps, device ms per launch,
     extras, parity_ok, cpu_baseline).  With stream2 the timed launches alternate over two streams (overlapping launches,
-    see timed_steps) and the classic one-stream protocol is measured first and reported in extras["single_stream"]."""
+    see timed_steps) and the classic one-stream protocol is measured first and reported in extras["single_stream"].
+    full=False (a plain run): the warm-up and the K timed launches of the protocol that makes `value`, nothing else --
+    parity_ok and cpu_baseline are None."""
     wl = Workload(ctx, kind, n, offset, dev, stream, nb=max(nb, 2 if stream2 is not None else 1))
+    if not full:
+        sts = [stream] if stream2 is None else [stream, stream2]
+        dt, kernel_ms = timed_steps(wl, steps, warmup, world, warm_s, streams=sts)
+        extra = {"streams": len(sts), "kernel": kernel_that_ran(kind, ctx.info(), len(sts) == 2)}
+        if wl.step_ms:
+            extra["per_launch_event_ms"] = step_stats(wl.step_ms, n, world)
+        else:
+            extra["device_ms_per_launch"] = kernel_ms
+        return wl, dt, kernel_ms, extra, None, None
     dt, kernel_ms = timed_steps(wl, steps, warmup, world, warm_s)
     extra = {"streams": 1, "clock": wl.clock, "kernel": kernel_that_ran(kind, ctx.info(), False)}
     if wl.step_ms:
@@ -1240,6 +1293,8 @@ def main():
     if args.warmup is None:
         args.warmup = 50 if args.workload == "fixed_base" else 3
     if args.native_multi:
+        if args.dump_outputs:
+            raise SystemExit("bench.py: --dump-outputs writes the outputs of the per-rank timed path, not of --native-multi")
         return run_native_multi(args)
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return launch_children(args)
@@ -1292,17 +1347,19 @@ def main():
         return stream_b if ns == 2 else None
 
     kind = args.workload
-    orc = get_oracle()
+    orc = get_oracle() if args.full else None
     one_gpu = world == 1
     parity = True
     global TELEMETRY
-    TELEMETRY = GpuTelemetry(local_rank).start()
+    TELEMETRY = GpuTelemetry(local_rank).start() if args.full else None
 
     # ---- headline: weak scaling, every rank its own block(s) of the global batch
     wl, dt, kernel_ms, extra, ok, cb = measure(ctx, kind, n, rank * n, dev, stream, args.steps, args.warmup, args.warmup_seconds,
                                                world, args.batches, orc, one_gpu and not args.no_cpu_baseline, rank,
-                                               stream2=second_stream(kind))
-    parity = parity and ok
+                                               stream2=second_stream(kind), full=args.full)
+    if args.dump_outputs and rank == 0:
+        extra["dumped_outputs"] = {"dir": args.dump_outputs, "shapes": wl.dump(args.steps - 1, args.dump_outputs)}
+    parity = parity and ok is not False
     dt_max = all_max(dt, world, red_dev)
     info = ctx.info()
     result = None
@@ -1323,19 +1380,29 @@ def main():
                        "streams": extra.get("streams", 1), "kernel": extra.get("kernel"),
                        "parallelism": "independent shards, one process per GPU, no data-path collective"},
         }
-        result["roofline"], ro = roofline_blocks(kind, kernel_ms, n, info, extra)
-        if ro:
-            result["roofline_overlapped"] = ro
+        if args.full:
+            result["roofline"], ro = roofline_blocks(kind, kernel_ms, n, info, extra)
+            if ro:
+                result["roofline_overlapped"] = ro
         result.update(extra)
-        ck = extra.get("clock") or {}
-        result["clock_mhz"] = ck.get("sclk_mhz")      # sampled across the timed region that produced `value`
-        result["socket_w"] = ck.get("socket_w")
-        vb = valu_block(kind, kernel_ms, n, info, one_stream_clock(extra))
-        if vb:
-            result["valu"] = vb
+        if args.full:
+            ck = extra.get("clock") or {}
+            result["clock_mhz"] = ck.get("sclk_mhz")      # sampled across the timed region that produced `value`
+            result["socket_w"] = ck.get("socket_w")
+            vb = valu_block(kind, kernel_ms, n, info, one_stream_clock(extra))
+            if vb:
+                result["valu"] = vb
         if cb:
             result["cpu_baseline"] = cb
     del wl
+    if not args.full:     # a plain run: the headline is all it measures, and nothing was compared with the oracle
+        devices = finish_world(world)
+        if rank == 0:
+            result["parity_sample_ok"] = None
+            result["devices"] = devices
+            publish(result)
+        ctx.close()
+        return 0
     hl = Headline(rank, result, float(os.environ.get("BJJ_BENCH_OPTIONAL_DEADLINE_S", "240")))
     hl.parity = parity
     try:
@@ -1521,6 +1588,11 @@ def optional_sections(args, hl, ctx, bjj, kind, n, rank, local_rank, world, dev,
     hl.parity = parity
 
     parity = all_and(parity, world, red_dev)
+    return parity, finish_world(world)
+
+
+def finish_world(world):
+    """the device of every rank (rank order); ends the process group"""
     if world > 1:
         devices = [None] * world
         dist.all_gather_object(devices, torch.cuda.current_device())
@@ -1528,7 +1600,7 @@ def optional_sections(args, hl, ctx, bjj, kind, n, rank, local_rank, world, dev,
         dist.destroy_process_group()
     else:
         devices = [torch.cuda.current_device()]
-    return parity, devices
+    return devices
 
 
 if __name__ == "__main__":

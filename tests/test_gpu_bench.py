@@ -7,6 +7,7 @@ import subprocess
 import sys
 import tempfile
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -41,7 +42,7 @@ def _run(extra, env_extra=None, timeout=1200):
 
 
 def test_bench_gpus_2_self_launch_shared_gpu():
-    r, j = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--warmup-seconds", "0", "--batch", "65536", "--batches", "2",
+    r, j = _run(["--full", "--gpus", "2", "--steps", "3", "--warmup", "1", "--warmup-seconds", "0", "--batch", "65536", "--batches", "2",
                  "--window-bits", "16", "--strong-total", str(1 << 18), "--no-cpu-baseline"],
                 {"BJJ_BENCH_SHARE_GPU": "1", "BJJ_BENCH_BACKEND": "gloo"})
     assert r.returncode == 0, r.stderr[-3000:]
@@ -59,7 +60,7 @@ def test_bench_gpus_2_self_launch_shared_gpu():
 
 def test_bench_gpus_3_ragged_strong_total():
     """three ranks and a total that does not divide: exact-size blocks out, verdicts back, every verdict checked on rank 0"""
-    r, j = _run(["--gpus", "3", "--steps", "2", "--warmup", "1", "--warmup-seconds", "0", "--batch", "20000", "--batches", "1",
+    r, j = _run(["--full", "--gpus", "3", "--steps", "2", "--warmup", "1", "--warmup-seconds", "0", "--batch", "20000", "--batches", "1",
                  "--window-bits", "12", "--strong-total", "100003", "--no-cpu-baseline", "--no-also"],
                 {"BJJ_BENCH_SHARE_GPU": "1", "BJJ_BENCH_BACKEND": "gloo"})
     assert r.returncode == 0, r.stderr[-3000:]
@@ -71,7 +72,7 @@ def test_bench_gpus_3_ragged_strong_total():
 def test_bench_gpus_8_node_shape_shared_gpu():
     """eight ranks -- the node size of the scaling bench and of BASELINE configs[4] -- sharing the one GPU: every rank its own
     context, a ragged total cut into 8 blocks, peer blocks in pieces, every gathered verdict checked on rank 0"""
-    r, j = _run(["--gpus", "8", "--steps", "2", "--warmup", "1", "--warmup-seconds", "0", "--batch", "8192", "--batches", "1",
+    r, j = _run(["--full", "--gpus", "8", "--steps", "2", "--warmup", "1", "--warmup-seconds", "0", "--batch", "8192", "--batches", "1",
                  "--window-bits", "12", "--strong-total", str((1 << 19) + 5), "--no-cpu-baseline", "--no-also"],
                 {"BJJ_BENCH_SHARE_GPU": "1", "BJJ_BENCH_BACKEND": "gloo"}, 1500)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -88,7 +89,7 @@ def test_bench_rejects_world_size_mismatch():
 
 
 def test_bench_one_gpu_line_has_every_block():
-    r, j = _run(["--steps", "20", "--warmup", "5", "--warmup-seconds", "0.2", "--batch", str(1 << 16), "--window-bits", "16",
+    r, j = _run(["--full", "--steps", "20", "--warmup", "5", "--warmup-seconds", "0.2", "--batch", str(1 << 16), "--window-bits", "16",
                  "--strong-total", str(1 << 18)])
     assert r.returncode == 0, r.stderr[-3000:]
     assert j["n_gpus"] == 1 and j["parity_sample_ok"] and j["roofline"]["frac"] > 0 and j["cpu_baseline"]["value"] > 0
@@ -160,7 +161,7 @@ def test_bench_one_gpu_line_has_every_block():
 def test_bench_point_add_and_compress_workloads():
     """the reference's remaining criterion cases (benches/bench_babyjubjub.rs:26-31, 40-41) as bench workloads"""
     for wl, unit in (("point_add", "point additions/s"), ("compress", "points/s")):
-        r, j = _run(["--workload", wl, "--steps", "10", "--warmup", "2", "--warmup-seconds", "0.1", "--batch", str(1 << 16), "--window-bits", "16",
+        r, j = _run(["--full", "--workload", wl, "--steps", "10", "--warmup", "2", "--warmup-seconds", "0.1", "--batch", str(1 << 16), "--window-bits", "16",
                      "--no-also", "--no-strong"])
         assert r.returncode == 0, r.stderr[-3000:]
         assert j["parity_sample_ok"] and j["unit"] == unit and j["roofline"]["achieved"] > 0 and j["cpu_baseline"]["value"] > 0
@@ -170,8 +171,68 @@ def test_bench_headline_survives_unfinished_optional_sections():
     """the watchdog of bench.Headline end to end: with a deadline the optional sections cannot meet, the line still carries the
     measured headline (value, roofline, parity of the headline's own oracle sample), a note, and the exit code is 4 (cut short:
     neither success nor the parity failure's 3)"""
-    r, j = _run(["--steps", "10", "--warmup", "2", "--warmup-seconds", "0.1", "--batch", str(1 << 16), "--window-bits", "16",
+    r, j = _run(["--full", "--steps", "10", "--warmup", "2", "--warmup-seconds", "0.1", "--batch", str(1 << 16), "--window-bits", "16",
                  "--strong-total", str(1 << 18), "--no-cpu-baseline"], {"BJJ_BENCH_OPTIONAL_DEADLINE_S": "0.001"}, 600)
     assert r.returncode == 4, r.stderr[-3000:]
     assert j["value"] > 0 and j["parity_sample_ok"] is True and j["roofline"]["frac"] > 0
     assert "abandoned" in j["optional_sections"] and "strong" not in j
+
+
+def test_bench_plain_run_measures_the_headline_only_and_dumps_its_outputs(oracle):
+    """a plain run (no --full): the contract's keys, `--steps` timed steps, none of the --full sections, and --dump-outputs writes
+    what the LAST timed step computed -- every row here (2^16 x 64 bytes fits the budget), byte-equal to the oracle"""
+    from babyjubjub_rs_amd import workload as w
+    n, steps = 1 << 16, 7
+    with tempfile.TemporaryDirectory() as td:
+        r, j = _run(["--gpus", "1", "--steps", str(steps), "--warmup", "2", "--warmup-seconds", "0.1", "--batch", str(n),
+                     "--window-bits", "16", "--dump-outputs", td])
+        assert r.returncode == 0, r.stderr[-3000:]
+        assert os.listdir(td) == ["points.npy"]
+        pts = np.load(os.path.join(td, "points.npy"))
+    c = r.compact
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in c, k
+    assert c["steps"] == steps and c["warmup"] == 2 and c["n_gpus"] == 1 and c["dtype"] == "u32" and c["higher_is_better"] is True
+    assert c["unit"] == "scalar mults/s" and abs(c["value"] - n * 1e3 / c["ms_per_step"]) < 1e-3 * c["value"]
+    for k in ("roofline", "cpu_baseline", "also", "strong", "valu", "clock_mhz", "single_stream"):
+        assert k not in c and k not in j, k
+    assert c["parity_sample_ok"] is None and j["streams"] == 2 and j["device_ms_per_launch"] > 0
+    assert c["config"]["kernel"] == "bjj_k_mul_fixed_base_2x256"
+    # the last timed launch is launch steps - 1: batch (steps - 1) % 4 of the rotation, SplitMix64 window offset b * n * 1009
+    b = (steps - 1) % j["config"]["resident_batches"]
+    assert pts.dtype == np.float32 and pts.shape == (n, 64) and j["dumped_outputs"]["shapes"] == {"points": [n, 64]}
+    got = pts.astype(np.uint8)
+    assert (got.astype(np.float32) == pts).all()
+    idx = np.arange(0, n, 61)
+    assert (got[idx] == oracle.mul_fixed_base(w.scalars_254(n, b * n * 1009)[idx])).all()
+
+
+def test_bench_dump_outputs_sampled_rows_and_verdicts(oracle):
+    """--dump-outputs on a batch whose outputs exceed the budget (a fixed seeded sample of rows), and on verify (every verdict:
+    1 for the valid signatures, 0 for the seeded 1-in-64 corrupted ones)"""
+    import bench
+    from babyjubjub_rs_amd import workload as w
+    n, steps = 1 << 18, 3
+    with tempfile.TemporaryDirectory() as td:
+        r, j = _run(["--steps", str(steps), "--warmup", "1", "--warmup-seconds", "0", "--batch", str(n), "--batches", "2",
+                     "--streams", "1", "--window-bits", "16", "--dump-outputs", td])
+        assert r.returncode == 0, r.stderr[-3000:]
+        pts = np.load(os.path.join(td, "points.npy"))
+    assert j["streams"] == 1 and j["per_launch_event_ms"]["median_ms"] > 0 and r.compact["steps"] == steps
+    m = bench.DUMP_BYTES // (4 * 64)
+    assert m < n and pts.shape == (m, 64) and pts.dtype == np.float32 and pts.nbytes <= 64 << 20
+    rows = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(n, m, replace=False))
+    b = (steps - 1) % 2
+    sel = np.arange(0, m, 509)
+    assert (pts[sel].astype(np.uint8) == oracle.mul_fixed_base(w.scalars_254(n, b * n * 1009)[rows[sel]])).all()
+
+    n, steps = 1 << 16, 5
+    with tempfile.TemporaryDirectory() as td:
+        r, j = _run(["--workload", "verify", "--steps", str(steps), "--warmup", "1", "--warmup-seconds", "0", "--batch", str(n),
+                     "--window-bits", "16", "--dump-outputs", td])
+        assert r.returncode == 0, r.stderr[-3000:]
+        v = np.load(os.path.join(td, "verdicts.npy"))
+    b = (steps - 1) % j["config"]["resident_batches"]
+    bad = (w.splitmix64(w.SEED_BAD, n, b * n * 1009) & np.uint64(63)) == 0
+    assert v.shape == (n,) and v.dtype == np.float32 and bad.any()
+    assert (v == (~bad).astype(np.float32)).all()

@@ -131,19 +131,7 @@ def test_every_public_item_of_the_reference_exists_with_the_same_signature():
         missing = sorted(k for k in want if k not in allow and have[k] < want[k])      # multiset: `pub x: Fr` occurs per struct
         assert missing == [], (mine, missing)
     assert len(api["lib.rs"]) >= 34 and len(api["utils.rs"]) == 6
-
-
-def test_reference_api_fixture_is_current():
-    """where the reference checkout exists (the build container), the fixture must equal a fresh extraction"""
-    import json
-    import pytest
-    if not os.path.isdir("/root/reference/src"):
-        pytest.skip("no reference checkout on this machine (the fixture is what travels)")
-    p = os.path.join(ROOT, "tests", "golden", "reference_pub_api.json")
-    before = open(p).read()
-    subprocess.run(["python3", os.path.join(ROOT, "tests", "golden", "make_reference_api.py")], check=True, stdout=subprocess.DEVNULL)
-    assert open(p).read() == before
-    assert json.loads(before)["lib.rs"][2]["item"] == "pub static ref Q: BigInt"
+    assert api["lib.rs"][2]["item"] == "pub static ref Q: BigInt"
 
 
 # ---- rust/src/utils.rs: a line-for-line Python model of its arithmetic, pinned to the reference's vectors and the oracle ----

@@ -7,8 +7,9 @@ process (fresh context, fresh clocks), and prints one row per run plus per-varia
 usage: tools/driver_protocol.py [--rounds 8] [--workload fixed_base] [--full] name=ENV1=V1,ENV2=V2[:extra bench args] ...
   a variant is `name=` followed by comma-separated environment assignments (may be empty) and, after a colon, extra bench.py
   arguments, e.g.   shipped=   v0=BJJ_K1_VARIANT=0   v1=BJJ_K1_VARIANT=1   one=:--streams 1   lib=BJJ_LIB_PATH=tools/ab_x.so
-  --full keeps the optional sections of the line (also / strong / cpu_baseline: ~90 s per run); without it they are
-  switched off -- the headline is measured first either way, under the identical protocol."""
+  Every run passes bench.py --full (the one-stream control and roofline this tool prints); --full here also keeps the optional
+  sections of the line (also / strong / cpu_baseline: ~90 s per run); without it they are switched off -- the headline is
+  measured first either way, under the identical protocol."""
 import json
 import os
 import statistics
@@ -45,7 +46,7 @@ def main():
     rows = {name: [] for name, _, _ in variants}
     for r in range(rounds):
         for name, env, extra in variants:
-            cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", steps, "--warmup", warmup]
+            cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", steps, "--warmup", warmup, "--full"]
             if workload != "fixed_base":
                 cmd += ["--workload", workload]
             if not full:

@@ -4,8 +4,8 @@
 # launches), then the --pmc passes of the same command (counters are per dispatch; the profiler serialises dispatches while it
 # counts), and the un-profiled line of the same command on the same box before and after.
 # usage: tools/profile_headline.sh <tag> [workload]     -> gpurun_out/<tag>/ts_<workload>_*
-#   fixed_base (default): the driver's exact command  `python3 bench.py --gpus 1 --steps 20 --warmup 5`  (+ --no-cpu-baseline)
-#   verify | var_base   : `python3 bench.py --workload <w> --steps 20 --warmup 3 --no-cpu-baseline --no-also --no-strong`
+#   fixed_base (default): the driver's exact command  `python3 bench.py --gpus 1 --steps 20 --warmup 5`  (+ --full --no-cpu-baseline)
+#   verify | var_base   : `python3 bench.py --workload <w> --steps 20 --warmup 3 --full --no-cpu-baseline --no-also --no-strong`
 TAG=${1:-r05}; WL=${2:-fixed_base}
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/$TAG; mkdir -p $OUT
@@ -14,9 +14,9 @@ export TMPDIR=/tmp
 python3 babyjubjub-rs_amd/srchash.py > $OUT/source_hash.txt
 python3 -c "import sys, json; sys.path.insert(0, 'babyjubjub-rs_amd'); import srchash; json.dump(srchash.kernel_hashes(), open('$OUT/code_hashes.json', 'w'), indent=1)"   # machine-code fingerprint of every kernel of the library that runs here
 if [ "$WL" = fixed_base ]; then
-  ARGS="bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline"; SHORT="--no-also --no-strong"
+  ARGS="bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline"; SHORT="--no-also --no-strong"
 else
-  ARGS="bench.py --workload $WL --steps 20 --warmup 3 --no-cpu-baseline --no-also --no-strong"; SHORT=""
+  ARGS="bench.py --workload $WL --steps 20 --warmup 3 --full --no-cpu-baseline --no-also --no-strong"; SHORT=""
 fi
 P=$OUT/ts_$WL
 echo "python3 $ARGS" > ${P}_command.txt

@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}; cd $R; O=gpurun_out/r06; mkdir -p $O
 PARTS=${@:-bench ab latency profiles scale}
 has() { [[ " $PARTS " == *" $1 "* ]]; }
 if has bench; then
-  python3 bench.py > $O/bench_default_stdout.txt 2> $O/bench_default_stderr.txt; echo "bench rc=$?"; cp bench_detail.json $O/bench_default_detail.json
+  python3 bench.py --full > $O/bench_default_stdout.txt 2> $O/bench_default_stderr.txt; echo "bench rc=$?"; cp bench_detail.json $O/bench_default_detail.json
   wc -c $O/bench_default_stdout.txt
 fi
 if has ab; then

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Developer session (round 6): the host-pointer rows of the bench line, the off-curve probe and the tests of the host pipeline on one box.
 R=${GRAFT_REPO_ROOT:-$(pwd)}; cd $R; O=gpurun_out/${1:-r06f}; mkdir -p $O
-python bench.py --no-cpu-baseline --no-strong > $O/bench_stdout.txt 2> $O/bench_stderr.txt; echo rc=$?
+python bench.py --full --no-cpu-baseline --no-strong > $O/bench_stdout.txt 2> $O/bench_stderr.txt; echo rc=$?
 python - <<PY
 import json
 d=json.load(open("bench_detail.json"))

@@ -7,5 +7,5 @@ for step in "$@"; do case $step in
   tests)   timeout 2400 python3 -m pytest tests -m gpu -q -x 2>&1 | tail -15 > $OUT/tests.txt; cat $OUT/tests.txt ;;
   ab)      timeout 900 python3 tools/fb_host_half_ab.py 23 2 10,15,16,17,18,19,20,21,22,23 > $OUT/fb_host_half_ab.txt 2>&1; cut -c1-420 $OUT/fb_host_half_ab.txt ;;
   latency) timeout 900 python3 tools/single_call_latency.py > $OUT/single_call_latency.txt 2>&1; cat $OUT/single_call_latency.txt ;;
-  bench)   timeout 900 python3 bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; cp bench_detail.json $OUT/bench_default_detail.json; cat $OUT/bench_default.json ;;
+  bench)   timeout 900 python3 bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; cp bench_detail.json $OUT/bench_default_detail.json; cat $OUT/bench_default.json ;;
 esac; done

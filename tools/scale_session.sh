@@ -33,7 +33,7 @@ if [ "$NG" -gt 1 ]; then
   # ---- (2) the driver's bench at 1, 2, 4, 8 ranks (one process per GPU, RCCL)
   for N in 1 2 4 8; do
     [ $N -le $NG ] || continue
-    step bench_n$N python3 bench.py --gpus $N --steps 20 --warmup 5
+    step bench_n$N python3 bench.py --gpus $N --steps 20 --warmup 5 --full
     last_json $O/bench_n$N.log > $P/${TAG}_scale_bench_n$N.json
   done
   DEVS=$(python3 -c "print(','.join(str(i) for i in range($NG)))")
@@ -47,7 +47,7 @@ else
   export BJJ_BENCH_WINDOW_BITS=16 BJJ_BENCH_TELEMETRY_MS=20
   step tests python3 -m pytest tests -m gpu -q -x -k "multi_block_arithmetic or multi_dev_form_rccl_one_device"
   for N in 1 2 8; do
-    BJJ_BENCH_SHARE_GPU=1 BJJ_BENCH_BACKEND=gloo step bench_n$N python3 bench.py --gpus $N --steps 5 --warmup 2 --batch 65536 --strong-total 262144 --no-cpu-baseline
+    BJJ_BENCH_SHARE_GPU=1 BJJ_BENCH_BACKEND=gloo step bench_n$N python3 bench.py --gpus $N --steps 5 --warmup 2 --batch 65536 --strong-total 262144 --full --no-cpu-baseline
     last_json $O/bench_n$N.log > $P/${TAG}_scale_dryrun_bench_n$N.json
   done
   step native_cases python3 tools/native_multi_cases.py --devices 0,0,0,0,0,0,0,0 --transport peer --window-bits 16 --per-gpu 32768 --out $P/${TAG}_scale_dryrun_native_cases.json

@@ -4,7 +4,7 @@ cd ${GRAFT_REPO_ROOT:-.}
 for WL in fixed_base verify var_base; do
   for B in 4096 65536 262144 1048576 4194304 16777216; do
     K=$(( B >= 4194304 ? 5 : 30 ))
-    python3 bench.py --workload $WL --batch $B --batches 2 --steps $K --warmup 3 --warmup-seconds 0.3 --no-cpu-baseline --no-also --no-strong 2>&1 >/dev/null | python3 -c "
+    python3 bench.py --workload $WL --batch $B --batches 2 --steps $K --warmup 3 --warmup-seconds 0.3 --full --no-cpu-baseline --no-also --no-strong 2>&1 >/dev/null | python3 -c "
 import sys, json
 for line in sys.stdin:
     if not line.startswith('bench_detail: {'): continue      # the full record (stderr); stdout carries the compact line
