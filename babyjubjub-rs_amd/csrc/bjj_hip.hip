@@ -177,9 +177,9 @@ struct bjj_ctx {
   // (CopyPool), never by the enqueueing thread
   hipStream_t s_in = nullptr, s_out = nullptr, stream2 = nullptr;
   std::vector<hipEvent_t> ev_in, ev_k, ev_out;   // per chunk of a super-batch (grown on demand)
-  std::vector<hipEvent_t> ev_dec;          // wire-format verifier through the pipeline: behind a chunk's decompressions (VerifyCompressedPipe)
-  hipEvent_t ev_tail = nullptr;            // behind the extra stages of a call (PipeExtra: verify's batch-wide exact launch)
-  u32* pipe_wl = nullptr;                  // verify through the pipeline: ONE list of off-curve items per super-batch (VerifyPipe)
+  std::vector<hipEvent_t> ev_mid;          // ... and behind a chunk's decompressions on its lane (the wire-format verifier's exact list)
+  hipEvent_t ev_tail = nullptr;            // behind the exact-list stage of a call (ExactListStage::close)
+  u32* pipe_wl = nullptr;                  // ONE list of the items that take the exact kernel, per super-batch (ExactListStage)
   size_t pipe_wl_items = 0;
   uint8_t* dstage = nullptr;   // device staging for one super-batch: every array contiguous
   size_t pipe_bytes = 0;
@@ -469,10 +469,10 @@ struct PipeSpec {
   const uint8_t* in[4]; size_t in_stride[4];
   uint8_t* out[4];      size_t out_stride[4];
   bool secret;          // inputs are key material: wipe the staging buffers when the call is done
-  struct PipeExtra* extra = nullptr;   // stages beside the chunk launches (below)
+  struct ExactListStage* exact = nullptr;   // the batch-wide exact list beside the chunk launches (below)
   bool out_at_end = false;             // outputs leave the device once, after everything (they are not final chunk by chunk)
   size_t first_chunk = 0, max_chunk = 0;   // chunk schedule of this entry point (items; 0 = the context's, which the environment overrides)
-  size_t extra_dev_per_item = 0;           // bytes of device staging per item for `extra` (PipeExtra::d_extra), beside the arrays
+  size_t extra_dev_per_item = 0;           // bytes of device staging per item for `exact` (ExactListStage::d_extra), beside the arrays
   // Kernel-bound calls whose launches are work-conserving among themselves (one tile / group per workgroup):
   //   tail_chunk            the LAST chunk has at most this many items (0 = no rule): its copy-out is the only one nothing hides
   //   last_on_priority_lane the lanes are the context's stream (normal priority) and stream2 (highest): the hardware serves the
@@ -490,7 +490,7 @@ struct PipeSpec {
   // pinned, the launches read them through the arrays' DEVICE MAPPINGS and there is no copy-in stage -- the first kernel starts at once
   // instead of behind a copy, and the chain of launches is no longer paced by the copy engine (43 GB/s over the small copies of a
   // schedule) but by the kernels.  For launch chains that outrun their copy-in: K1, whose 2^20 items are 0.55 ms of kernel behind
-  // 0.77 ms of copy-in (profiles/r06_fb_zero_copy_in.txt).  Not with `extra` stages (they wait for copies).
+  // 0.77 ms of copy-in (profiles/r06_fb_zero_copy_in.txt).  Not with an `exact` stage (its scans wait for copies).
   bool zero_copy_in = false;
   // K1 chunk launches (fixed base, public keys): a launch of K1 is persistent -- every lane walks its items, then ONE epilogue per
   // workgroup (inversion, phase 2) -- and its ramp, epilogue and tail cost about one round of multiplications (~70 us) whatever
@@ -505,24 +505,38 @@ struct PipeSpec {
   // output byte once and read none of it back (csrc/k_small.hip).  0 = never.
   size_t small_direct_max = 0;
 };
-// Work of a pipelined call that does not belong to ONE chunk.  All three run on the calling thread while it enqueues:
-//   begin          once per super-batch, before the first copy; d_in / d_out = the staging arrays of the whole super-batch
-//   chunk_arrived  behind the H2D of items lo .. lo+cnt-1 (ev_in of the chunk has been recorded: make a stream wait for it)
-//   all_arrived    behind the last chunk; whatever it enqueues is covered by ev_tail, which the call waits for before it copies
-//                  `out_at_end` outputs and returns
-//   all_launched   behind the last chunk's launch -- for stages that need what the chunks' own launches produce (the wire-format verifier scans
-//                  points its chunks' launches have decompressed); a stage that uses it records ev_tail there instead of in all_arrived
-//   finish         last: every copy of the super-batch has landed in the caller's arrays (host_out = where its outputs begin), every
-//                  stream of the pipeline and ev_tail are done -- host-side work on the results
-struct PipeExtra {
-  void* d_extra = nullptr;     // n * PipeSpec::extra_dev_per_item bytes of the super-batch's device staging (set before begin)
-  bool zero_copy = false;      // begin's d_out[] are the device mappings of the caller's pinned output arrays (PipeSpec::zero_copy_out)
-  virtual int begin(size_t n, void** d_in, void** d_out) = 0;
-  virtual int chunk_arrived(size_t lo, size_t cnt, hipEvent_t arrived) = 0;
-  virtual int all_arrived(hipEvent_t ev_tail) = 0;
-  virtual int all_launched(hipEvent_t ev_tail) { (void)ev_tail; return BJJ_OK; }   // behind the LAST chunk's launch (what it enqueues is covered by ev_tail, too)
-  virtual int finish(uint8_t* const* host_out, size_t n) { (void)host_out; (void)n; return BJJ_OK; }
-  virtual ~PipeExtra() {}
+// The batch-wide exact list of a host-pointer call: variable base (off-curve points), the verifiers (off-curve pk / R) and the wire-format
+// verifier (the same, after decompression).  An item of that kind takes the exact kernel, ~3x as long as a bulk item and strictly serial per
+// lane; a chunk launch that carried its own would last as long as they do and hold its lane.  So each chunk's bulk launch skips them, and ONE
+// exact launch over ONE list serves the super-batch, on the first scratch set's scan stream, beside the bulk launches.  The pipeline calls,
+// on the calling thread while it enqueues:
+//   open        once per super-batch, before the first copy: the list, reset on the scan stream; d_in / d_out = the super-batch's arrays
+//   decompress  wire format only, per chunk, on its lane behind its H2D: pk, R and s into d_extra; the pipeline records ev_mid behind it
+//   scan        per chunk: the scan stream waits for `ready` (the chunk's ev_in, or its ev_mid), then appends the chunk's items to the list
+//   close       once, behind the last chunk's launch (every scan is enqueued): the exact launch, then a pass over the whole batch where
+//               there is one -- it writes output bytes the bulk launches write too, so it waits for every lane's last bulk launch
+//               (bulk_done) -- then ev_tail, which the call waits for before it copies `out_at_end` outputs and returns
+//   finish      last, every copy landed (host_out = where the super-batch's outputs begin): variable base with staged outputs lays K6's
+//               compact results over their slots in the caller's array
+struct ExactListStage {
+  enum Kind { VAR_BASE, VERIFY, VERIFY_COMPRESSED };
+  bjj_ctx* const c;
+  const Kind kind;
+  bool schnorr = false;              // VERIFY
+  int sc_words = 0;                  // VAR_BASE: 4-byte words per scalar
+  size_t n = 0;                      // items of the super-batch
+  uint8_t* in[4] = {};               // its inputs on the device: pts, scalars | pk, r, s, msg | pk32, sig64, msg
+  uint8_t* out = nullptr;            // its output: the staging, or (zero_copy) the device mapping of the caller's pinned array
+  uint8_t* d_extra = nullptr;        // n * PipeSpec::extra_dev_per_item bytes of the super-batch's staging
+  bool zero_copy = false;
+  uint8_t *pk = nullptr, *r = nullptr, *s = nullptr, *msg = nullptr;   // what the verify kernels read: in[], or what decompress wrote to d_extra
+  uint8_t *f_pk = nullptr, *f_r = nullptr;                               // VERIFY_COMPRESSED: the decompression flags (d_extra)
+  ExactListStage(bjj_ctx* c_, Kind k) : c(c_), kind(k) {}
+  int open(size_t n, void* const* d_in, void* const* d_out, uint8_t* d_extra, bool zero_copy);
+  int decompress(size_t lo, size_t cnt, hipStream_t lane);
+  int scan(size_t lo, size_t cnt, hipEvent_t ready);
+  int close(const hipEvent_t* bulk_done, size_t lanes);
+  int finish(uint8_t* host_out);
 };
 static size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 static size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
@@ -638,6 +652,8 @@ static int ensure_pipe(bjj_ctx* c, size_t chunks, size_t dev_bytes, size_t in_ri
       HIPCK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); c->ev_k.push_back(e);
       e = nullptr;
       HIPCK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); c->ev_out.push_back(e);
+      e = nullptr;
+      HIPCK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); c->ev_mid.push_back(e);
     }
   } catch (...) { return set_err(BJJ_E_NOMEM, "host-pointer pipeline: out of host memory"); }
   if (dev_bytes > c->pipe_bytes) {
@@ -742,7 +758,7 @@ static int run_super_batch_body(bjj_ctx* c, size_t n, const PipeSpec& sp, const 
   const bool chunk_out_ring = out_ring && !sp.out_at_end;   // pageable outputs travel chunk by chunk through the ring
   // zero-copy outputs: every output array pinned AND mapped into the device's address space
   uint8_t* mapped_out[4] = {nullptr, nullptr, nullptr, nullptr};
-  const bool small_direct = sp.small_direct_max && n <= sp.small_direct_max && nchunks == 1 && !sp.extra && c->pipe_small_direct;
+  const bool small_direct = sp.small_direct_max && n <= sp.small_direct_max && nchunks == 1 && !sp.exact && c->pipe_small_direct;
   bool zc = (sp.zero_copy_out || small_direct) && !out_ring && sp.n_out > 0 && !sp.out_at_end && c->pipe_zero_copy;
   for (int i = 0; i < sp.n_out && zc; i++) {
     void* dp = nullptr;
@@ -752,7 +768,7 @@ static int run_super_batch_body(bjj_ctx* c, size_t n, const PipeSpec& sp, const 
   uint8_t* mapped_in[4] = {nullptr, nullptr, nullptr, nullptr};
   // Calls of one or two chunks: every chunk.  Longer calls: the FIRST chunk only -- the head of the chain of launches starts at once instead
   // of behind its copy, and the copy-in of the chunks behind it, which keeps the two lanes' launches out of phase, starts earlier too.
-  bool zi = (sp.zero_copy_in || small_direct) && !in_ring && sp.n_in > 0 && !sp.extra && c->pipe_zero_copy_in;
+  bool zi = (sp.zero_copy_in || small_direct) && !in_ring && sp.n_in > 0 && !sp.exact && c->pipe_zero_copy_in;
   for (int i = 0; i < sp.n_in && zi; i++) {
     void* dp = nullptr;
     if (!in_direct[i] || ((uintptr_t)sp.in[i] & 15u) || hipHostGetDevicePointer(&dp, (void*)sp.in[i], 0) != hipSuccess || !dp) { (void)hipGetLastError(); zi = false; }   // (the kernels move 16-byte words)
@@ -763,13 +779,11 @@ static int run_super_batch_body(bjj_ctx* c, size_t n, const PipeSpec& sp, const 
   const size_t zi_chunks = !zi ? 0 : (nchunks <= 2 ? nchunks : (size_t)zi_first_env);
   c->last_host_zero_copy = (zc ? 1u : 0u) | (zi_chunks == nchunks ? 2u : 0u);
   c->k1_half_now = sp.k1_half && nchunks >= 2;
-  if (sp.extra) {
-    void* bi[4]; void* bo[4];
+  if (sp.exact) {
+    void* bi[4] = {}; void* bo[4] = {};
     for (int i = 0; i < sp.n_in; i++) bi[i] = c->dstage + d_in_off[i];
     for (int i = 0; i < sp.n_out; i++) bo[i] = zc ? (void*)mapped_out[i] : (void*)(c->dstage + d_out_off[i]);
-    sp.extra->zero_copy = zc;
-    sp.extra->d_extra = sp.extra_dev_per_item ? c->dstage + d_extra_off : nullptr;
-    int rc = sp.extra->begin(n, bi, bo); if (rc) return rc;
+    int rc = sp.exact->open(n, bi, bo, sp.extra_dev_per_item ? c->dstage + d_extra_off : nullptr, zc); if (rc) return rc;
   }
   *chunks_out += (u32)nchunks;
   CopyPool* pool = c->pool;
@@ -829,18 +843,26 @@ static int run_super_batch_body(bjj_ctx* c, size_t n, const PipeSpec& sp, const 
                            cnt * sp.in_stride[i], hipMemcpyHostToDevice, c->s_in));
     if (!zi) HIPCK(hipEventRecord(c->ev_in[ch], c->s_in));
     tmark(1 + 3 * ch, c->s_in);                                // H2D done
-    if (sp.extra) {
-      int r = sp.extra->chunk_arrived(lo, cnt, c->ev_in[ch]); if (r) return r;
-      if (ch + 1 == nchunks) { r = sp.extra->all_arrived(c->ev_tail); if (r) return r; }
-    }
     hipStream_t lane = ((ch + lane_flip) & 1) ? c->stream2 : c->stream;
     if (!zi) HIPCK(hipStreamWaitEvent(lane, c->ev_in[ch], 0));
+    if (sp.exact) {   // the chunk's items onto the exact list: behind their copy, or behind their decompressions on the lane
+      hipEvent_t ready = c->ev_in[ch];
+      if (sp.exact->kind == ExactListStage::VERIFY_COMPRESSED) {
+        int r = sp.exact->decompress(lo, cnt, lane); if (r) return r;
+        HIPCK(hipEventRecord(c->ev_mid[ch], lane));
+        ready = c->ev_mid[ch];
+      }
+      int r = sp.exact->scan(lo, cnt, ready); if (r) return r;
+    }
     void* d_in[4]; void* d_out[4];
     for (int i = 0; i < sp.n_in; i++) d_in[i] = (zi ? mapped_in[i] : c->dstage + d_in_off[i]) + lo * sp.in_stride[i];
     for (int i = 0; i < sp.n_out; i++) d_out[i] = (zc ? mapped_out[i] : c->dstage + d_out_off[i]) + lo * sp.out_stride[i];
     int r = launch(d_in, d_out, cnt, (void*)lane); if (r) return r;
-    if (sp.extra && ch + 1 == nchunks) { r = sp.extra->all_launched(c->ev_tail); if (r) return r; }
     HIPCK(hipEventRecord(c->ev_k[ch], lane));                  // behind a kernel: its completion signal, no extra packet
+    if (sp.exact && ch + 1 == nchunks) {   // every scan is enqueued; chunks ch and ch - 1 are the last of their lanes
+      const hipEvent_t bulk_done[2] = {c->ev_k[ch], ch ? c->ev_k[ch - 1] : nullptr};
+      r = sp.exact->close(bulk_done, ch ? 2 : 1); if (r) return r;
+    }
     tmark(2 + 3 * ch, lane);                                   // kernels done
     tr("kernels enqueued", ch);
     return BJJ_OK;
@@ -893,7 +915,7 @@ static int run_super_batch_body(bjj_ctx* c, size_t n, const PipeSpec& sp, const 
     { int r = drain_kernels(true, nchunks); if (r) return r; }
     if (chunk_out_ring) for (size_t ch = harvested; ch < nchunks; ch++) { int r = finish_out(ch); if (r) return r; }
     if (chunk_out_ring) for (size_t ch = 0; ch < nchunks; ch++) pool->wait(&g_out[ch]);
-    if (sp.extra) { HIPCK(hipEventSynchronize(c->ev_tail)); tr("extra stages complete", nchunks); }
+    if (sp.exact) { HIPCK(hipEventSynchronize(c->ev_tail)); tr("exact list complete", nchunks); }
     if (sp.out_at_end) {   // the whole output arrays, once: pinned -> directly, pageable -> ring slot 0 -> workers
       for (int i = 0; i < sp.n_out; i++)
         HIPCK(hipMemcpyAsync(out_direct[i] ? sp.out[i] : c->pin_out[0] + r_out_off[i], c->dstage + d_out_off[i], n * sp.out_stride[i], hipMemcpyDeviceToHost, c->s_out));
@@ -910,7 +932,7 @@ static int run_super_batch_body(bjj_ctx* c, size_t n, const PipeSpec& sp, const 
   };
   int rc = body();
   tr("all chunks finished", nchunks);
-  if (!rc && sp.extra) { rc = sp.extra->finish(sp.out, n); tr("extra stages finished on the host", nchunks); }
+  if (!rc && sp.exact) { rc = sp.exact->finish(sp.out[0]); tr("exact list finished on the host", nchunks); }
   if (trace && !rc) {
     for (size_t ch = 0; ch < nchunks; ch++) {
       float t[3] = {0, 0, 0};
@@ -921,7 +943,7 @@ static int run_super_batch_body(bjj_ctx* c, size_t n, const PipeSpec& sp, const 
   for (hipEvent_t e : tev) if (e) hipEventDestroy(e);
   if (rc) {   // error path: nothing may still be writing into the caller's memory or reading the rings when we return
     hipStreamSynchronize(c->s_in); hipStreamSynchronize(c->stream); hipStreamSynchronize(c->stream2); hipStreamSynchronize(c->s_out);
-    if (sp.extra) hipDeviceSynchronize();   // whatever the extra stages had enqueued on their own streams
+    if (sp.exact) hipDeviceSynchronize();   // whatever the exact-list stage had enqueued on the scan stream
     (void)hipGetLastError();
     if (pool) for (size_t ch = 0; ch < nchunks; ch++) { pool->wait(&g_in[ch]); pool->wait(&g_out[ch]); }
   }
@@ -1035,7 +1057,7 @@ static void ctx_destroy(bjj_ctx* c) {
   if (c->ev_tail) hipEventDestroy(c->ev_tail);
   if (c->pipe_wl) hipFree(c->pipe_wl);
   for (hipEvent_t e : c->ev_k) hipEventDestroy(e);
-  for (hipEvent_t e : c->ev_dec) hipEventDestroy(e);
+  for (hipEvent_t e : c->ev_mid) hipEventDestroy(e);
   if (c->err_words) hipHostFree(c->err_words);
   if (c->vb_seen) hipHostFree(c->vb_seen);
   if (c->patch_host) hipHostFree(c->patch_host);
@@ -1468,14 +1490,123 @@ static int var_base_launch(bjj_ctx* c, const void* d_pts, const void* d_scalars,
   else LAUNCHCK(bjjk::mul_var_base_exact(st, c->cus * 4, pts, sc, sc_words, (uint8_t*)d_out, S->slow, nullptr, seen), "variable-base (exact)");
   SET_LEAVE(c);
 }
-// ---- variable base through the host-pointer pipeline: the cure verify got in round 5 (VerifyPipe below) -----------------------
-//   per chunk, behind its H2D:  the on-curve scan of its points on the priority stream, appending batch-wide indices to ONE list;
-//                               K2 over its items on its lane -- K2 skips an off-curve item by itself and never writes its slot
-//   behind the last scan:       ONE K6 launch over the list on the priority stream, results COMPACT beside the list (d_extra): a
-//                               chunk's outputs leave the device when its K2 is done, long before K6 is
-//   when everything has landed: the host lays the few exact results over their slots in the caller's array
-// Before: K6 behind K2 in EVERY chunk's lane -- one off-curve point in 4 096 cost 2^20 items on pinned memory +71 % (15.9 ->
-// 27.3 ms, profiles/r05_var_base_offcurve.txt).
+// ---- the exact list of the host-pointer pipeline (ExactListStage, declared beside PipeSpec) ----------------------------------------
+// Before it, variable base ran K6 behind K2 in EVERY chunk's lane -- one off-curve point in 4 096 cost 2^20 items on pinned memory +71 %
+// (15.9 -> 27.3 ms, profiles/r05_var_base_offcurve.txt) -- and a verify chunk carried its own exact groups: it lasted at least as long as
+// they do, 6.6 ms for the first 2^15 items instead of 2.3, and the next chunk of its lane waited behind it; 2^20 verifications of
+// BASELINE configs[3] (1 in 64 corrupted, half of those off the curve) took 25 ms on pinned host memory against 18.7 ms on device
+// pointers (profiles/r05_host_verify_exact_split.txt).  Per kind:
+//   VAR_BASE           scan: the on-curve scan of the chunk's points.  Bulk: K2, which skips an off-curve item by itself and never writes
+//                      its slot.  Exact: ONE K6 launch, its results COMPACT beside the list (d_extra) -- a chunk's outputs leave the device
+//                      when its K2 is done, long before K6 is -- which the host lays over their slots (finish).  Zero-copy outputs: K6
+//                      stores straight into the caller's mapped array, and d_extra is K2's phase-1 stash.
+//   VERIFY             scan: the on-curve scan of pk and R.  Bulk: a bulk workgroup recognises and skips an off-curve item by itself.
+//                      Exact: ONE launch whose few workgroups take the next slots that free up; it shares the first scratch set's slot
+//                      queue with that set's bulk launches -- the queue holds a slot for every workgroup that can be resident, whatever
+//                      launch it belongs to.  The verdicts leave once, after both (PipeSpec::out_at_end: 1 byte per item).
+//   VERIFY_COMPRESSED  as VERIFY, on what the chunk's decompressions wrote to d_extra (162 B per item).  After the exact launch ONE pass
+//                      writes verdict 2 where pk or R did not decompress (such an item decompresses to (0, 0), which is off the curve: it
+//                      is on the list).  The bulk launches write verdict 0 for every item with msg > Q, whatever its points, so the pass
+//                      runs behind them as well -- as on device pointers, where it follows the launch on the caller's stream.
+int ExactListStage::open(size_t n_, void* const* d_in, void* const* d_out, uint8_t* extra, bool zc) {
+  n = n_;
+  for (int i = 0; i < 4; i++) in[i] = (uint8_t*)d_in[i];
+  out = (uint8_t*)d_out[0];
+  d_extra = extra;
+  zero_copy = zc;
+  if (kind == VERIFY) { pk = in[0]; r = in[1]; s = in[2]; msg = in[3]; }
+  if (kind == VERIFY_COMPRESSED) { pk = d_extra; r = pk + n * 64; s = r + n * 64; f_pk = s + n * 32; f_r = f_pk + n; msg = in[2]; }
+  ScratchSet* S = &c->set[0];
+  { int rc_ = ensure_scan_stream(S); if (rc_) return rc_; }
+  if (kind != VAR_BASE) {
+    // the verifiers' exact launch works in this set's tables without being one of its calls (set_enter / set_leave): whatever used the set
+    // last on another stream -- a variable-base launch a caller has enqueued and not waited for lays ITS tables over the same memory --
+    // must be done first.  Afterwards only this call's own bulk launches touch the set (slot queue), and the call does not return before
+    // the exact launch has completed (ev_tail).
+    int rc_ = ensure_scratch(c, S, 1); if (rc_) return rc_;      // the set's tables and slot queues exist
+    rc_ = set_enter(c, S, S->scan_stream); if (rc_) return rc_;
+  }
+  if (n > c->pipe_wl_items) {
+    if (c->pipe_wl) { HIPCK(hipDeviceSynchronize()); HIPCK(hipFree(c->pipe_wl)); c->pipe_wl = nullptr; c->pipe_wl_items = 0; }
+    HIPCK(hipMalloc((void**)&c->pipe_wl, (n + 16) * sizeof(u32)));
+    c->pipe_wl_items = n;
+  }
+  if (kind == VAR_BASE) LAUNCHCK(bjjk::var_base_list_reset(S->scan_stream, c->pipe_wl), "variable-base list");
+  else LAUNCHCK(bjjk::verify_list_reset(S->scan_stream, c->pipe_wl), "verify list");
+  return BJJ_OK;
+}
+int ExactListStage::decompress(size_t lo, size_t cnt, hipStream_t lane) {
+  const int g = grid_for(c, cnt, c->occ_decomp);
+  LAUNCHCK(bjjk::decompress_points(lane, g, in[0] + lo * 32, 32, cnt, pk + lo * 64, f_pk + lo, nullptr), "decompress(pk)");
+  LAUNCHCK(bjjk::decompress_points(lane, g, in[1] + lo * 64, 64, cnt, r + lo * 64, f_r + lo, s + lo * 32), "decompress(sig)");
+  return BJJ_OK;
+}
+int ExactListStage::scan(size_t lo, size_t cnt, hipEvent_t ready) {
+  hipStream_t xs = c->set[0].scan_stream;
+  HIPCK(hipStreamWaitEvent(xs, ready, 0));
+  if (kind == VAR_BASE)
+    LAUNCHCK(bjjk::var_base_scan(xs, grid_for(c, cnt, c->occ_vb_scan, 64), in[0], lo, lo + cnt, c->pipe_wl), "variable-base scan");
+  else
+    LAUNCHCK(bjjk::verify_scan_range(xs, grid_for(c, cnt, c->occ_scan, 64) * 64 / bjjk::verify_scan_block(), pk, r, msg, lo, lo + cnt, c->pipe_wl),
+             "verify scan");
+  return BJJ_OK;
+}
+int ExactListStage::close(const hipEvent_t* bulk_done, size_t lanes) {
+  ScratchSet* S = &c->set[0];
+  hipStream_t xs = S->scan_stream;
+  if (kind == VAR_BASE) {
+    LAUNCHCK(bjjk::mul_var_base_exact(xs, c->cus * 4, in[0], in[1], sc_words, zero_copy ? out : nullptr, c->pipe_wl, zero_copy ? nullptr : d_extra,
+                                      &c->vb_seen[BJJ_SCRATCH_SETS]), "variable-base (exact)");
+  } else {
+    c->rings_used = true;
+    LAUNCHCK(bjjk::verify_main(xs, 1, 0, schnorr, c->table, c->W, c->nwin, pk, r, s, msg, n, out, S->vb_tables, c->pipe_wl, S->slotq,
+                               S->slot_cap | ((u32)c->xccs << 16), bjjk::VERIFY_EXACT), "verify (exact)");
+  }
+  if (kind == VERIFY_COMPRESSED) {   // output bytes the bulk launches write too: behind every lane's last one
+    for (size_t l = 0; l < lanes; l++) HIPCK(hipStreamWaitEvent(xs, bulk_done[l], 0));
+    LAUNCHCK(bjjk::merge_codec_flags(xs, grid_for(c, n, 8), out, f_pk, f_r, n), "merge_codec_flags");
+  }
+  HIPCK(hipEventRecord(c->ev_tail, xs));
+  return BJJ_OK;
+}
+int ExactListStage::finish(uint8_t* host_out) {
+  if (kind != VAR_BASE || zero_copy) return BJJ_OK;
+  const size_t cnt = __atomic_load_n(&c->vb_seen[BJJ_SCRATCH_SETS], __ATOMIC_ACQUIRE);   // K6 is done (ev_tail): its count is in
+  if (!cnt) return BJJ_OK;
+  if (cnt > n) return set_err(BJJ_E_HIP, "variable base: the exact list is longer than the batch");
+  const size_t need = cnt * 68;
+  if (need > c->patch_host_bytes) {
+    if (c->patch_host) { HIPCK(hipHostFree(c->patch_host)); c->patch_host = nullptr; c->patch_host_bytes = 0; }
+    const size_t want = need < ((size_t)1 << 16) ? (size_t)1 << 16 : need + need / 2;
+    HIPCK(hipHostMalloc((void**)&c->patch_host, want, hipHostMallocDefault));
+    c->patch_host_bytes = want;
+  }
+  HIPCK(hipMemcpyAsync(c->patch_host, d_extra, cnt * 64, hipMemcpyDeviceToHost, c->s_out));
+  HIPCK(hipMemcpyAsync(c->patch_host + cnt * 64, c->pipe_wl + 8, cnt * 4, hipMemcpyDeviceToHost, c->s_out));
+  HIPCK(hipStreamSynchronize(c->s_out));
+  const u32* idx = (const u32*)(c->patch_host + cnt * 64);
+  for (size_t j = 0; j < cnt; j++) {
+    if (idx[j] >= n) return set_err(BJJ_E_HIP, "variable base: index out of range on the exact list");
+    memcpy(host_out + (size_t)idx[j] * 64, c->patch_host + j * 64, 64);
+  }
+  return BJJ_OK;
+}
+// Does a host-pointer call take the split form, bulk launches per chunk beside ONE exact launch over the exact list?  Not for a call of
+// fewer than first + first / 2 items: that is one chunk, a device-pointer launch with copies around it (a single `verify` or
+// Point::mul_scalar, src/lib.rs:395 / 149, is such a call) -- its exact groups start first inside the launch, nothing waits behind them,
+// and three launches instead of two would only add latency.  Not when the persistent verify form (BJJ_VERIFY_DISPATCH=0) or K6 behind K2
+// (BJJ_VB_SPLIT=0) is forced -- one launch per chunk, exact items included -- nor when the round-5 per-chunk form is (developer, and the
+// tests' cross-check: BJJ_PIPE_VERIFY_SPLIT=0 / BJJ_PIPE_VAR_BASE_SPLIT=0).
+static int exact_split_applies(bjj_ctx* c, bool var_base, size_t n, size_t first_chunk, bool* split) {
+  { int rc_ = ensure_pipe(c, 0, 0, 0, 0); if (rc_) return rc_; }   // the knobs: the chunk schedule of the environment
+  static const bool verify_per_chunk = [] { const char* e = getenv("BJJ_PIPE_VERIFY_SPLIT"); return e && e[0] == '0'; }();
+  static const bool var_base_per_chunk = [] { const char* e = getenv("BJJ_PIPE_VAR_BASE_SPLIT"); return e && e[0] == '0'; }();
+  const size_t first = c->pipe_env_schedule ? c->pipe_first : first_chunk;
+  const bool forced_off = var_base ? var_base_per_chunk || c->vb_split == 0 : verify_per_chunk || c->verify_mode == 0;
+  *split = !forced_off && n >= first + first / 2;
+  return BJJ_OK;
+}
+// ---- variable base through the host-pointer pipeline ---------------------------------------------------------------------------
 static int var_base_bulk_launch(bjj_ctx* c, const void* d_pts, const void* d_scalars, size_t scalar_bytes, size_t n, void* d_out, uint8_t* xy, void* stream) {
   SET_ENTER(c, stream, n, false);
   // one tile per workgroup, whatever else is in flight: the chunks' launches are then work-conserving among themselves -- a
@@ -1490,76 +1621,18 @@ static int var_base_bulk_launch(bjj_ctx* c, const void* d_pts, const void* d_sca
                                    S->scratch, S->vb_tables, nullptr, S->slotq2, S->slot_cap2 | ((u32)c->xccs << 16), xy), "variable base (bulk)");
   SET_LEAVE(c);
 }
-struct VarBasePipe : PipeExtra {
-  bjj_ctx* c;
-  int sc_words;
-  const uint8_t *pts = nullptr, *scalars = nullptr;
-  uint8_t* out = nullptr;      // zero_copy: the device mapping of the caller's pinned output array (K6 writes its items' slots itself)
-  size_t n = 0;
-  VarBasePipe(bjj_ctx* c_, size_t scalar_bytes) : c(c_), sc_words((int)(scalar_bytes / 4)) {}
-  int begin(size_t n_, void** d_in, void** d_out) override {
-    out = (uint8_t*)d_out[0];
-    n = n_;
-    pts = (const uint8_t*)d_in[0]; scalars = (const uint8_t*)d_in[1];
-    ScratchSet* S = &c->set[0];
-    { int rc_ = ensure_scan_stream(S); if (rc_) return rc_; }
-    if (n > c->pipe_wl_items) {
-      if (c->pipe_wl) { HIPCK(hipDeviceSynchronize()); HIPCK(hipFree(c->pipe_wl)); c->pipe_wl = nullptr; c->pipe_wl_items = 0; }
-      HIPCK(hipMalloc((void**)&c->pipe_wl, (n + 16) * sizeof(u32)));
-      c->pipe_wl_items = n;
-    }
-    LAUNCHCK(bjjk::var_base_list_reset(S->scan_stream, c->pipe_wl), "variable-base list");
-    return BJJ_OK;
-  }
-  int chunk_arrived(size_t lo, size_t cnt, hipEvent_t arrived) override {
-    ScratchSet* S = &c->set[0];
-    HIPCK(hipStreamWaitEvent(S->scan_stream, arrived, 0));
-    LAUNCHCK(bjjk::var_base_scan(S->scan_stream, grid_for(c, cnt, c->occ_vb_scan, 64), pts, lo, lo + cnt, c->pipe_wl), "variable-base scan");
-    return BJJ_OK;
-  }
-  int all_arrived(hipEvent_t ev_tail) override {
-    ScratchSet* S = &c->set[0];
-    // zero-copy: d_extra is K2's stash and K6 stores straight into the caller's array; else d_extra takes K6's results compactly
-    LAUNCHCK(bjjk::mul_var_base_exact(S->scan_stream, c->cus * 4, pts, scalars, sc_words, zero_copy ? out : nullptr, c->pipe_wl,
-                                      zero_copy ? nullptr : (uint8_t*)d_extra, &c->vb_seen[BJJ_SCRATCH_SETS]), "variable-base (exact)");
-    HIPCK(hipEventRecord(ev_tail, S->scan_stream));
-    return BJJ_OK;
-  }
-  int finish(uint8_t* const* host_out, size_t) override {
-    const size_t cnt = __atomic_load_n(&c->vb_seen[BJJ_SCRATCH_SETS], __ATOMIC_ACQUIRE);   // K6 is done (ev_tail): its count is in
-    if (!cnt || zero_copy) return BJJ_OK;
-    if (cnt > n) return set_err(BJJ_E_HIP, "variable base: the exact list is longer than the batch");
-    const size_t need = cnt * 68;
-    if (need > c->patch_host_bytes) {
-      if (c->patch_host) { HIPCK(hipHostFree(c->patch_host)); c->patch_host = nullptr; c->patch_host_bytes = 0; }
-      const size_t want = need < ((size_t)1 << 16) ? (size_t)1 << 16 : need + need / 2;
-      HIPCK(hipHostMalloc((void**)&c->patch_host, want, hipHostMallocDefault));
-      c->patch_host_bytes = want;
-    }
-    HIPCK(hipMemcpyAsync(c->patch_host, d_extra, cnt * 64, hipMemcpyDeviceToHost, c->s_out));
-    HIPCK(hipMemcpyAsync(c->patch_host + cnt * 64, c->pipe_wl + 8, cnt * 4, hipMemcpyDeviceToHost, c->s_out));
-    HIPCK(hipStreamSynchronize(c->s_out));
-    const u32* idx = (const u32*)(c->patch_host + cnt * 64);
-    for (size_t j = 0; j < cnt; j++) {
-      if (idx[j] >= n) return set_err(BJJ_E_HIP, "variable base: index out of range on the exact list");
-      memcpy(host_out[0] + (size_t)idx[j] * 64, c->patch_host + j * 64, 64);
-    }
-    return BJJ_OK;
-  }
-};
 static int var_base_host(bjj_ctx* c, const uint8_t* pts, const uint8_t* scalars, size_t scalar_bytes, size_t n, uint8_t* out) {
   PipeSpec sp = {2, 1, {pts, scalars}, {64, scalar_bytes}, {out}, {64}, false};
   if (scalar_bytes == 32 && c->k2_variant < 0) sp.small_direct_max = small_direct_items(c->vb_quad_max);
   sp.first_chunk = (size_t)1 << 16;   // 14 ms of kernels over 3 ms of copies: a 2^15-item launch holds its lane for a whole round with a quarter of the chip
   sp.max_chunk = (size_t)1 << 18;
-  static const bool per_chunk = [] { const char* e = getenv("BJJ_PIPE_VAR_BASE_SPLIT"); return e && e[0] == '0'; }();   // developer: the round-5 form
-  { ENTER_DEVICE(c->device); int rc_ = ensure_pipe(c, 0, 0, 0, 0); if (rc_) return rc_; }
-  const size_t first = c->pipe_env_schedule ? c->pipe_first : sp.first_chunk;
-  // a call of ONE chunk is a device-pointer launch with copies around it (a single Point::mul_scalar, src/lib.rs:149, is such a call)
-  if (per_chunk || c->vb_split == 0 || n < first + first / 2)
+  bool split = false;
+  { int rc_ = exact_split_applies(c, true, n, sp.first_chunk, &split); if (rc_) return rc_; }
+  if (!split)
     return run_pipelined(c, n, sp, [&](void** i, void** o, size_t cnt, void* st) { return var_base_launch(c, i[0], i[1], scalar_bytes, cnt, o[0], st, "bjj_mul_var_base"); });
-  VarBasePipe vp(c, scalar_bytes);
-  sp.extra = &vp;
+  ExactListStage ex(c, ExactListStage::VAR_BASE);
+  ex.sc_words = (int)(scalar_bytes / 4);
+  sp.exact = &ex;
   sp.extra_dev_per_item = 64;         // K6's compact results (as many as there are items, at worst) -- or, zero-copy, K2's phase-1 stash
   sp.last_on_priority_lane = true;
   // Pinned output array: the kernels store into it themselves (64 MB of results over the 15 ms the kernels take anyway) -- no copy-out
@@ -1569,8 +1642,8 @@ static int var_base_host(bjj_ctx* c, const uint8_t* pts, const uint8_t* scalars,
   if (c->pipe_zero_copy && c->k2_variant != 0 && !c->force_staged && host_range_pinned(out, n * 64)) { sp.zero_copy_out = true; sp.max_chunk = (size_t)1 << 24; }   // (the stash apart exists for the tiles)
   else { sp.tail_chunk = (size_t)1 << 16; sp.max_chunk = (size_t)1 << 18; }
   return run_pipelined(c, n, sp, [&](void** i, void** o, size_t cnt, void* st) {
-    const size_t lo = (size_t)((const uint8_t*)i[0] - vp.pts) / 64;           // this chunk's first item within the super-batch
-    return var_base_bulk_launch(c, i[0], i[1], scalar_bytes, cnt, o[0], vp.zero_copy ? (uint8_t*)vp.d_extra + lo * 64 : nullptr, st); });
+    const size_t lo = (size_t)((uint8_t*)i[0] - ex.in[0]) / 64;           // this chunk's first item within the super-batch
+    return var_base_bulk_launch(c, i[0], i[1], scalar_bytes, cnt, o[0], ex.zero_copy ? ex.d_extra + lo * 64 : nullptr, st); });
 }
 int bjj_mul_var_base_dev(bjj_ctx* c, const void* d_pts, const void* d_scalars, size_t n, void* d_out, void* stream) {
   return var_base_launch(c, d_pts, d_scalars, 32, n, d_out, stream, "bjj_mul_var_base_dev");
@@ -1648,20 +1721,9 @@ int bjj_eddsa_verify_dev(bjj_ctx* c, const void* d_pk, const void* d_r, const vo
                          void* d_ok, void* stream) {
   return verify_launch(c, false, d_pk, d_r, d_s, d_msg, n, d_ok, stream, "bjj_eddsa_verify_dev");
 }
-// ---- verify through the host-pointer pipeline -----------------------------------------------------------------------
-// Items whose pk or R is off the curve take the reference's exact formula sequence, ~3x as long as a bulk item and strictly
-// serial per lane (k_verify.hip).  A device-pointer launch starts them first and they are long done when the bulk is; a
-// CHUNK of the pipeline that carries its own exact items lasts at least as long as they do -- 6.6 ms for the first 2^15 items
-// instead of 2.3 -- and the next chunk of its lane waits behind it: 2^20 verifications of BASELINE configs[3] (1 in 64
-// corrupted, half of those off the curve) took 25 ms on pinned host memory against 18.7 ms on device pointers
-// (profiles/r05_host_verify_exact_split.txt).  Here the two kinds of work are separate launches:
-//   per chunk, behind its H2D:  the on-curve scan of its items on the priority stream, appending batch-wide indices to ONE list
-//                               the bulk launch of its items on its lane (no scan needed: a bulk workgroup recognises and skips
-//                               an off-curve item by itself)
-//   behind the last scan:       ONE exact launch over the list, on the priority stream (its few workgroups take the next slots
-//                               that free up); it shares the first scratch set's slot queue with that set's bulk launches -- the
-//                               queue holds a slot for every workgroup that can be resident, whatever launch it belongs to
-// The verdicts leave once, after both (PipeSpec::out_at_end: 1 byte per item).
+// ---- the verifiers through the host-pointer pipeline -------------------------------------------------------------------------
+// Items whose pk or R is off the curve take the reference's exact formula sequence, ~3x as long as a bulk item and strictly serial per
+// lane (k_verify.hip): the pipeline takes them out of the chunks into the exact list (ExactListStage::VERIFY above).
 static int verify_bulk_launch(bjj_ctx* c, bool schnorr, const void* d_pk, const void* d_r, const void* d_s, const void* d_msg, size_t n,
                               void* d_ok, void* stream) {
   SET_ENTER(c, stream, n, false);
@@ -1672,148 +1734,44 @@ static int verify_bulk_launch(bjj_ctx* c, bool schnorr, const void* d_pk, const 
                              bjjk::VERIFY_BULK), "verify (bulk)");
   SET_LEAVE(c);
 }
-struct VerifyPipe : PipeExtra {
-  bjj_ctx* c;
-  bool schnorr;
-  const uint8_t *pk = nullptr, *r = nullptr, *s = nullptr, *msg = nullptr;
-  uint8_t* ok = nullptr;
-  size_t n = 0;
-  VerifyPipe(bjj_ctx* c_, bool schnorr_) : c(c_), schnorr(schnorr_) {}
-  int begin(size_t n_, void** d_in, void** d_out) override {
-    n = n_;
-    pk = (const uint8_t*)d_in[0]; r = (const uint8_t*)d_in[1]; s = (const uint8_t*)d_in[2]; msg = (const uint8_t*)d_in[3];
-    ok = (uint8_t*)d_out[0];
-    ScratchSet* S = &c->set[0];
-    { int rc_ = ensure_scratch(c, S, 1); if (rc_) return rc_; }      // the set's tables and slot queues exist
-    { int rc_ = ensure_scan_stream(S); if (rc_) return rc_; }
-    // the exact launch works in this set's tables without being one of its calls (set_enter / set_leave): whatever used the set
-    // last on another stream -- a variable-base launch a caller has enqueued and not waited for lays ITS tables over the same
-    // memory -- must be done first.  Afterwards only this call's own bulk launches touch the set (slot queue), and the call
-    // does not return before the exact launch has completed (ev_tail).
-    { int rc_ = set_enter(c, S, S->scan_stream); if (rc_) return rc_; }
-    if (n > c->pipe_wl_items) {
-      if (c->pipe_wl) { HIPCK(hipDeviceSynchronize()); HIPCK(hipFree(c->pipe_wl)); c->pipe_wl = nullptr; c->pipe_wl_items = 0; }
-      HIPCK(hipMalloc((void**)&c->pipe_wl, (n + 16) * sizeof(u32)));
-      c->pipe_wl_items = n;
-    }
-    LAUNCHCK(bjjk::verify_list_reset(S->scan_stream, c->pipe_wl), "verify list");
-    return BJJ_OK;
-  }
-  int chunk_arrived(size_t lo, size_t cnt, hipEvent_t arrived) override {
-    ScratchSet* S = &c->set[0];
-    HIPCK(hipStreamWaitEvent(S->scan_stream, arrived, 0));
-    const int grid = grid_for(c, cnt, c->occ_scan, 64) * 64 / bjjk::verify_scan_block();
-    LAUNCHCK(bjjk::verify_scan_range(S->scan_stream, grid, pk, r, msg, lo, lo + cnt, c->pipe_wl), "verify scan");
-    return BJJ_OK;
-  }
-  int all_arrived(hipEvent_t ev_tail) override {
-    ScratchSet* S = &c->set[0];
-    c->rings_used = true;
-    LAUNCHCK(bjjk::verify_main(S->scan_stream, 1, 0, schnorr, c->table, c->W, c->nwin, pk, r, s, msg, n, ok, S->vb_tables, c->pipe_wl, S->slotq,
-                               S->slot_cap | ((u32)c->xccs << 16), bjjk::VERIFY_EXACT), "verify (exact)");
-    HIPCK(hipEventRecord(ev_tail, S->scan_stream));
-    return BJJ_OK;
-  }
-};
 static int verify_host(bjj_ctx* c, bool schnorr, const uint8_t* pk, const uint8_t* r, const uint8_t* s, const uint8_t* msg, size_t n, uint8_t* ok) {
   PipeSpec sp = {4, 1, {pk, r, s, msg}, {64, 64, 32, 32}, {ok}, {1}, false};
   if (c->verify_mode < 0) sp.small_direct_max = small_direct_items(c->verify_small_max);
-  static const bool per_chunk = [] { const char* e = getenv("BJJ_PIPE_VERIFY_SPLIT"); return e && e[0] == '0'; }();   // developer: the round-5 form
-  // a call of ONE chunk is a device-pointer launch with copies around it: its exact groups start first inside the launch, nothing
-  // waits behind them, and three launches instead of two would only add latency (a single `verify`, src/lib.rs:395, is such a call)
-  { ENTER_DEVICE(c->device); int rc_ = ensure_pipe(c, 0, 0, 0, 0); if (rc_) return rc_; }
-  const size_t first = c->pipe_env_schedule ? c->pipe_first : (size_t)1 << 16;
-  const bool one_chunk = n < first + first / 2;
-  sp.first_chunk = first;
-  sp.max_chunk = (size_t)1 << 19;
-  if (c->verify_mode == 0 || per_chunk || one_chunk)   // (the persistent form, when forced, is one launch per chunk, exact items included)
-    return run_pipelined(c, n, sp, [&](void** i, void** o, size_t cnt, void* st) {
-      return schnorr ? bjj_schnorr_verify_dev(c, i[0], i[1], i[2], i[3], cnt, o[0], st) : bjj_eddsa_verify_dev(c, i[0], i[1], i[2], i[3], cnt, o[0], st); });
-  VerifyPipe vp(c, schnorr);
-  sp.extra = &vp;
-  sp.out_at_end = true;
   // 18 ms of kernels against 3.9 ms of H2D for 2^20 items: the copy-out never bounds this call, what costs is the ramp (the
   // chip is part empty until the first chunks have arrived) and every launch's partly empty last round -- fewer, larger chunks
   // than the copy-bound default (2^16 / 2^19: 19.17 ms, 2^15 / 2^18: 19.36 ms; profiles/r05_host_verify_exact_split.txt)
+  sp.first_chunk = (size_t)1 << 16;
+  sp.max_chunk = (size_t)1 << 19;
+  bool split = false;
+  { int rc_ = exact_split_applies(c, false, n, sp.first_chunk, &split); if (rc_) return rc_; }
+  if (!split)
+    return run_pipelined(c, n, sp, [&](void** i, void** o, size_t cnt, void* st) {
+      return schnorr ? bjj_schnorr_verify_dev(c, i[0], i[1], i[2], i[3], cnt, o[0], st) : bjj_eddsa_verify_dev(c, i[0], i[1], i[2], i[3], cnt, o[0], st); });
+  ExactListStage ex(c, ExactListStage::VERIFY);
+  ex.schnorr = schnorr;
+  sp.exact = &ex;
+  sp.out_at_end = true;
   return run_pipelined(c, n, sp, [&](void** i, void** o, size_t cnt, void* st) { return verify_bulk_launch(c, schnorr, i[0], i[1], i[2], i[3], cnt, o[0], st); });
 }
-// ---- the wire-format verifier through the pipeline (round 6) ------------------------------------------------------------------
-// bjj_eddsa_verify_compressed on host pointers used to be the device entry point per chunk: decompressions, scan and a launch that carried the
-// chunk's own exact groups -- the form the plain verifiers left in round 5 -- and with the pipeline's default chunks it took 31.7 ms for 2^20
-// signatures of which 1 in 64 is corrupted (39.5 ms with the 2^17-item cap of round 6) against 23.5 ms for one device-pointer launch.  Now, like
-// VerifyPipe, with one more stage in front:
-//   per chunk, on its lane:     decompress pk, decompress R (+ s) into the super-batch's staging (d_extra: 162 B per item), an event;
-//                               behind the event, on the priority stream, the on-curve scan of the chunk into ONE batch-wide list;
-//                               the bulk launch of the chunk on its lane
-//   behind the last chunk:      ONE exact launch over the list, then ONE pass that writes verdict 2 where pk or R did not decompress (such an item
-//                               decompresses to (0, 0), which is off the curve: it is on the list, the exact launch writes it last, the pass after it)
-struct VerifyCompressedPipe : PipeExtra {
-  bjj_ctx* c;
-  const uint8_t *pk32 = nullptr, *sig64 = nullptr, *msg = nullptr;
-  uint8_t *ok = nullptr, *pk_xy = nullptr, *r_xy = nullptr, *s32 = nullptr, *f_pk = nullptr, *f_r = nullptr;
-  size_t n = 0, launched = 0;
-  explicit VerifyCompressedPipe(bjj_ctx* c_) : c(c_) {}
-  int begin(size_t n_, void** d_in, void** d_out) override {
-    n = n_; launched = 0;
-    pk32 = (const uint8_t*)d_in[0]; sig64 = (const uint8_t*)d_in[1]; msg = (const uint8_t*)d_in[2];
-    ok = (uint8_t*)d_out[0];
-    pk_xy = (uint8_t*)d_extra; r_xy = pk_xy + n * 64; s32 = r_xy + n * 64; f_pk = s32 + n * 32; f_r = f_pk + n;
-    ScratchSet* S = &c->set[0];
-    { int rc_ = ensure_scratch(c, S, 1); if (rc_) return rc_; }
-    { int rc_ = ensure_scan_stream(S); if (rc_) return rc_; }
-    { int rc_ = set_enter(c, S, S->scan_stream); if (rc_) return rc_; }     // (as VerifyPipe: the exact launch works in this set's tables)
-    if (n > c->pipe_wl_items) {
-      if (c->pipe_wl) { HIPCK(hipDeviceSynchronize()); HIPCK(hipFree(c->pipe_wl)); c->pipe_wl = nullptr; c->pipe_wl_items = 0; }
-      HIPCK(hipMalloc((void**)&c->pipe_wl, (n + 16) * sizeof(u32)));
-      c->pipe_wl_items = n;
-    }
-    LAUNCHCK(bjjk::verify_list_reset(S->scan_stream, c->pipe_wl), "verify list");
-    return BJJ_OK;
-  }
-  int chunk_arrived(size_t, size_t, hipEvent_t) override { return BJJ_OK; }
-  int all_arrived(hipEvent_t) override { return BJJ_OK; }
-  // one chunk on its lane (called by the pipeline's launch closure): items lo .. lo + cnt - 1 of the super-batch
-  int launch_chunk(size_t lo, size_t cnt, hipStream_t lane) {
-    ScratchSet* S = &c->set[0];
-    const int g = grid_for(c, cnt, c->occ_decomp);
-    LAUNCHCK(bjjk::decompress_points(lane, g, pk32 + lo * 32, 32, cnt, pk_xy + lo * 64, f_pk + lo, nullptr), "decompress(pk)");
-    LAUNCHCK(bjjk::decompress_points(lane, g, sig64 + lo * 64, 64, cnt, r_xy + lo * 64, f_r + lo, s32 + lo * 32), "decompress(sig)");
-    try {
-      while (c->ev_dec.size() <= launched) { hipEvent_t e = nullptr; HIPCK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); c->ev_dec.push_back(e); }
-    } catch (...) { return set_err(BJJ_E_NOMEM, "host-pointer pipeline: out of host memory"); }
-    hipEvent_t ev = c->ev_dec[launched++];
-    HIPCK(hipEventRecord(ev, lane));
-    HIPCK(hipStreamWaitEvent(S->scan_stream, ev, 0));
-    const int sg = grid_for(c, cnt, c->occ_scan, 64) * 64 / bjjk::verify_scan_block();
-    LAUNCHCK(bjjk::verify_scan_range(S->scan_stream, sg, pk_xy, r_xy, msg, lo, lo + cnt, c->pipe_wl), "verify scan");
-    return verify_bulk_launch(c, false, pk_xy + lo * 64, r_xy + lo * 64, s32 + lo * 32, msg + lo * 32, cnt, ok + lo, (void*)lane);
-  }
-  int all_launched(hipEvent_t ev_tail) override {
-    ScratchSet* S = &c->set[0];
-    c->rings_used = true;
-    LAUNCHCK(bjjk::verify_main(S->scan_stream, 1, 0, false, c->table, c->W, c->nwin, pk_xy, r_xy, s32, msg, n, ok, S->vb_tables, c->pipe_wl, S->slotq,
-                               S->slot_cap | ((u32)c->xccs << 16), bjjk::VERIFY_EXACT), "verify (exact)");
-    LAUNCHCK(bjjk::merge_codec_flags(S->scan_stream, grid_for(c, n, 8), ok, f_pk, f_r, n), "merge_codec_flags");
-    HIPCK(hipEventRecord(ev_tail, S->scan_stream));
-    return BJJ_OK;
-  }
-};
+// The wire-format verifier (round 6) used to be the device entry point per chunk: decompressions, scan and a launch that carried the chunk's
+// own exact groups -- the form the plain verifiers left in round 5 -- and with the pipeline's default chunks it took 31.7 ms for 2^20
+// signatures of which 1 in 64 is corrupted (39.5 ms with the 2^17-item cap of round 6) against 23.5 ms for one device-pointer launch.  Now the
+// plain verifiers' form with the chunk's decompressions in front (ExactListStage::VERIFY_COMPRESSED).
 static int verify_compressed_host(bjj_ctx* c, const uint8_t* pk32, const uint8_t* sig64, const uint8_t* msg, size_t n, uint8_t* ok) {
   PipeSpec sp = {3, 1, {pk32, sig64, msg}, {32, 64, 32}, {ok}, {1}, false};
-  static const bool per_chunk = [] { const char* e = getenv("BJJ_PIPE_VERIFY_SPLIT"); return e && e[0] == '0'; }();   // developer: the form until round 6
-  { ENTER_DEVICE(c->device); int rc_ = ensure_pipe(c, 0, 0, 0, 0); if (rc_) return rc_; }
-  const size_t first = c->pipe_env_schedule ? c->pipe_first : (size_t)1 << 16;
-  sp.first_chunk = first;
+  sp.first_chunk = (size_t)1 << 16;
   sp.max_chunk = (size_t)1 << 19;          // the verifiers' schedule: 23 ms of kernels hide 2.5 ms of copies several times over
-  if (c->verify_mode == 0 || per_chunk || n < first + first / 2)
+  bool split = false;
+  { int rc_ = exact_split_applies(c, false, n, sp.first_chunk, &split); if (rc_) return rc_; }
+  if (!split)
     return run_pipelined(c, n, sp, [&](void** i, void** o, size_t cnt, void* st) { return bjj_eddsa_verify_compressed_dev(c, i[0], i[1], i[2], cnt, o[0], st); });
-  VerifyCompressedPipe vp(c);
-  sp.extra = &vp;
+  ExactListStage ex(c, ExactListStage::VERIFY_COMPRESSED);
+  sp.exact = &ex;
   sp.extra_dev_per_item = 162;             // decompressed pk (64) + R (64) + s (32) + the two decompression flags
   sp.out_at_end = true;
-  return run_pipelined(c, n, sp, [&](void** i, void** o, size_t cnt, void* st) {
-    (void)o;
-    return vp.launch_chunk((size_t)((const uint8_t*)i[0] - vp.pk32) / 32, cnt, (hipStream_t)st); });
+  return run_pipelined(c, n, sp, [&](void** i, void** o, size_t cnt, void* st) {   // the chunk's decompressions are on its lane already
+    const size_t lo = (size_t)((uint8_t*)i[0] - ex.in[0]) / 32;
+    return verify_bulk_launch(c, false, ex.pk + lo * 64, ex.r + lo * 64, ex.s + lo * 32, i[2], cnt, o[0], st); });
 }
 int bjj_schnorr_verify_dev(bjj_ctx* c, const void* d_pk, const void* d_r, const void* d_s, const void* d_msg, size_t n,
                            void* d_ok, void* stream) {

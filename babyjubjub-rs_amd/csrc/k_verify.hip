@@ -217,7 +217,7 @@ hipError_t verify_main(hipStream_t st, int mode, int grid, bool schnorr, const u
   // part (VERIFY_BOTH / VERIFY_BULK / VERIFY_EXACT, bjj_launch.hpp): the two kinds of workgroup of this form are independent --
   // a bulk workgroup skips the items of the list, an exact workgroup touches nothing else -- so they can be two launches.  The
   // host-pointer pipeline uses that: a chunk's bulk launch lasts as long as its items take, not as long as the ~3x longer exact
-  // items among them, and ONE exact launch serves the whole batch (bjj_hip.hip: VerifyPipe).
+  // items among them, and ONE exact launch serves the whole batch (bjj_hip.hip: ExactListStage).
   const size_t nchunks = (n + 63) / 64;
   const unsigned exact_wgs = part == VERIFY_BULK ? 0u : (unsigned)(nchunks < 4096 ? nchunks : 4096);      // most of them find nothing on the list and exit at once
   const unsigned bulk_wgs = part == VERIFY_EXACT ? 0u : (unsigned)(nchunks < 32768 ? nchunks : 32768);    // one 64-item chunk each up to 2^21 items, strided beyond

@@ -435,7 +435,7 @@ def test_kernel_form_follows_pattern_and_state(oracle):
 def test_host_verify_behind_an_unfinished_launch_that_owns_the_first_scratch_set(oracle):
     """The exact launch of a host-pointer verification of several chunks works in the first scratch set's per-lane tables without being one
     of the set's calls.  Variable-base launches the caller has enqueued on streams of their own and NOT waited for lay their tile tables
-    over the same memory: the verification queues its exact launch behind the set's last foreign launch (VerifyPipe::begin).  The scenario
+    over the same memory: the verification queues its exact launch behind the set's last foreign launch (ExactListStage::open).  The scenario
     -- both scratch sets owned by launches in flight -- is run and all three results are compared with runs that had the GPU to
     themselves.  (Whether a missing wait shows depends on how the hardware interleaves the launches: a build without it passed this test on
     the boxes of round 5, its exact launch running beside both others for 22 ms.  The wait is required by the set protocol all the same.)"""

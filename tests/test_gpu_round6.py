@@ -453,3 +453,51 @@ def test_host_verify_compressed_across_chunks_every_verdict(oracle, mem):
         assert (got[sel] == oracle.verify_compressed(pkc[sel], sig[sel], msgs[sel])).all()
     finally:
         ctx.close()
+
+
+@pytest.mark.parametrize("mem", ["pinned", "pageable"])
+def test_host_verify_compressed_msg_over_q_with_a_point_that_does_not_decompress(mem):
+    """An item with msg > Q AND a pk or R that does not decompress: the bulk launch of its chunk writes verdict 0 (msg > Q), the flag pass
+    after the exact launch writes 2 over it -- on host pointers only if the pass runs behind every lane's last bulk launch.  Three chunks,
+    such items in each of them and most in the LAST one (whose bulk launch outlives the exact launch); every verdict against ONE
+    device-pointer launch of the same inputs, those items at exactly 2."""
+    import babyjubjub_rs_amd as bjj
+    import torch
+    ctx = bjj.Context(0, 16)
+    try:
+        n = (1 << 16) + (1 << 17) + 70001                               # chunks [0, 2^16), [2^16, 3 * 2^16), [3 * 2^16, n)
+        rng = np.random.default_rng(0x6d736751)
+        keys = rng.integers(0, 256, (n, 32), dtype=np.uint8)
+        msgs = rng.integers(0, 256, (n, 32), dtype=np.uint8)
+        msgs[:, 31] &= 0x1f
+        pkc = ctx.public_keys_compressed(keys)
+        sig, okf = ctx.sign_compressed(keys, msgs)
+        assert okf.all()
+        last = 3 << 16
+        no_r = np.unique(np.concatenate([rng.choice(last, 40, replace=False), last + rng.choice(n - last, 400, replace=False), [last, n - 1]]))
+        no_pk = np.unique(np.concatenate([rng.choice(last, 40, replace=False), last + rng.choice(n - last, 400, replace=False), [n - 2]]))
+        no_pk = np.setdiff1d(no_pk, no_r)
+        msgs[no_r, 31] = 0xff; sig[no_r, :32] = 0xff                   # msg > Q, R does not decompress
+        msgs[no_pk, 31] = 0xff; pkc[no_pk, :32] = 0xff                 # msg > Q, pk does not decompress (y >= r)
+        over_q = rng.choice(n, 300, replace=False)
+        over_q = np.setdiff1d(over_q, np.concatenate([no_r, no_pk]))
+        msgs[over_q, 31] = 0xff                                        # msg > Q alone: verdict 0
+        dev = torch.device("cuda", 0)
+        d = [torch.from_numpy(a.reshape(-1)).to(dev) for a in (pkc, sig, msgs)]
+        d_ok = torch.full((n,), 0xEE, dtype=torch.uint8, device=dev)
+        ctx.eddsa_verify_compressed_dev(d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), n, d_ok.data_ptr())
+        ctx.sync()
+        want = d_ok.cpu().numpy()
+        assert (want[no_r] == 2).all() and (want[no_pk] == 2).all() and (want[over_q] == 0).all()
+        alloc = ctx.host_empty if mem == "pinned" else (lambda nb: np.zeros(nb, np.uint8))
+        bufs = []
+        for a in (pkc, sig, msgs):
+            b = alloc(a.size); b[:] = a.reshape(-1); bufs.append(b)
+        ok = alloc(n); ok[:] = 0xCD
+        assert ctx.lib.bjj_eddsa_verify_compressed(ctx.handle, bufs[0].ctypes.data, bufs[1].ctypes.data, bufs[2].ctypes.data, ctypes.c_size_t(n), ok.ctypes.data) == 0
+        i = ctx.info()
+        assert i.last_host_chunks == 3 and i.last_verify_dispatch == 1
+        got = np.asarray(ok).copy()
+        assert (got == want).all(), (int((got != want).sum()), np.nonzero(got != want)[0][:8], got[got != want][:8], want[got != want][:8])
+    finally:
+        ctx.close()

@@ -99,7 +99,7 @@ def test_soak_all_entry_points(gpu_ctx, oracle, seed):
 def test_soak_host_verify_across_chunks(gpu_ctx, oracle, seed):
     """The verifiers on host pointers at sizes of several chunks: a call's off-curve items run as ONE launch beside the chunks'
     bulk launches, its scans append to one batch-wide list, and that launch shares a slot queue with one lane's bulk launches
-    (bjj_hip.hip: VerifyPipe).  Random size, random density of off-curve pk / R (none ... 1 in 3), each array pinned or pageable
+    (bjj_hip.hip: ExactListStage).  Random size, random density of off-curve pk / R (none ... 1 in 3), each array pinned or pageable
     at random; every verdict against ONE device-pointer launch of the same inputs (exact groups inside the launch), a sample
     that contains off-curve items against the oracle."""
     import torch
