@@ -41,6 +41,7 @@ EXPORTED_SYMBOLS = (
     "bjj_host_alloc", "bjj_host_free", "bjj_host_register", "bjj_host_unregister", "bjj_host_is_pinned",
     "bjj_mul_fixed_base_compressed", "bjj_public_keys_compressed", "bjj_sign_compressed",
     "bjj_mul_fixed_base_compressed_dev", "bjj_public_keys_compressed_dev", "bjj_sign_compressed_dev",
+    "bjj_msm", "bjj_msm_dev",
 )
 
 
@@ -171,6 +172,8 @@ def load():
     lib.bjj_mul_fixed_base_compressed_dev.argtypes = [vp, vp, sz, vp, vp]
     lib.bjj_public_keys_compressed_dev.argtypes = [vp, vp, sz, vp, vp]
     lib.bjj_sign_compressed_dev.argtypes = [vp, vp, vp, sz, vp, vp, vp]
+    lib.bjj_msm.argtypes = [vp, vp, vp, sz, ci, vp, ctypes.POINTER(ctypes.c_int64)]
+    lib.bjj_msm_dev.argtypes = [vp, vp, vp, sz, ci, vp, vp, vp]
     # multi-GPU
     pd = ctypes.POINTER(ctypes.c_double)
     lib.bjj_multi_init.argtypes = [ctypes.POINTER(ci), ci, ci, ctypes.POINTER(vp)]

@@ -259,6 +259,24 @@ class Context:
         self._ck(self.lib.bjj_point_add(self.handle, a.ctypes.data, b.ctypes.data, n, out.ctypes.data), "bjj_point_add")
         return out.reshape(n, 64)
 
+    def msm(self, points, scalars, window_bits=0):
+        """Q = sum k_i * P_i as ONE (1, 64) record (bjj_msm): the fold of P_i.mul_scalar(k_i) with PointProjective::add from the
+        identity, then affine() (lib.rs:149-164, 88-131, 70-85).  n == 0 gives (0, 1).  An off-curve point raises BjjError naming
+        the smallest such index (the library returns (0, 0) and that index as data).  window_bits: 0 = the library's choice, 4..20
+        forces the bucket width."""
+        a = _as_u8(points, 64, "points")
+        s = _as_u8(scalars, 32, "scalars")
+        n = a.size // 64
+        if s.size != n * 32:
+            raise BjjError("msm: %d points but %d scalars" % (n, s.size // 32))
+        out = np.empty(64, dtype=np.uint8)
+        first = ctypes.c_int64(-1)
+        self._ck(self.lib.bjj_msm(self.handle, a.ctypes.data if n else None, s.ctypes.data if n else None, n, int(window_bits),
+                                  out.ctypes.data, ctypes.byref(first)), "bjj_msm")
+        if first.value != -1:
+            raise BjjError("msm: point %d is not on the curve" % first.value)
+        return out.reshape(1, 64)
+
     def set_signer_constant_time(self, on=True):
         """signer hardening: public_keys / sign / sign_schnorr scan a small 4-bit table instead of indexing the big one
         with secret digits -- no secret-dependent address or branch; bit-identical results, ~2x slower sign"""
@@ -389,6 +407,11 @@ class Context:
 
     def compress_points_dev(self, d_pts, n, d_out, stream=0):
         self._ck(self.lib.bjj_compress_points_dev(self.handle, d_pts, n, d_out, stream), "bjj_compress_points_dev")
+
+    def msm_dev(self, d_pts, d_scalars, n, d_out, d_first_off_curve, window_bits=0, stream=0):
+        """bjj_msm_dev: 64-byte result and the int64 status word (-1, or the smallest off-curve index) written by the device"""
+        self._ck(self.lib.bjj_msm_dev(self.handle, d_pts, d_scalars, n, int(window_bits), d_out, d_first_off_curve, stream),
+                 "bjj_msm_dev")
 
     def point_add_dev(self, d_p, d_q, n, d_out, stream=0):
         self._ck(self.lib.bjj_point_add_dev(self.handle, d_p, d_q, n, d_out, stream), "bjj_point_add_dev")
@@ -747,3 +770,16 @@ def verify_batch(pk, r_b8, s, msg, ctx=None):
 
 def point_add_batch(p, q, ctx=None):
     return (ctx or default_context()).point_add(p, q)
+
+
+def msm(points, scalars, ctx=None):
+    """sum of points[i].mul_scalar(scalars[i]) as a Point (bjj_msm); points: Points or (x, y) pairs, scalars: ints < 2^256.
+    BjjError for an off-curve point (the reference fold over non-group elements has no meaning here)."""
+    pts = [(p.x, p.y) if isinstance(p, Point) else tuple(p) for p in points]
+    sc = [int(k) for k in scalars]
+    if len(pts) != len(sc):
+        raise BjjError("msm: %d points but %d scalars" % (len(pts), len(sc)))
+    if any(k < 0 or k >> 256 for k in sc):
+        raise BjjError("msm: scalars are 256-bit unsigned integers")
+    x, y = _ints((ctx or default_context()).msm(pts, sc), 2)[0]
+    return Point(x, y)

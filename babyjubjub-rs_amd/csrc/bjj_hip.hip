@@ -109,6 +109,8 @@ struct ScratchSet {
   size_t codec_items = 0;
   uint8_t* xy = nullptr;       // K1 with compressed output: n * 64 B, the phase-1 stash of X, Y (the 32-byte output slot cannot hold it)
   size_t xy_items = 0;
+  uint8_t* msm = nullptr;      // bjj_msm: one block per call laid out by bjjk::msm_layout (+ the host form's copies of the inputs)
+  size_t msm_bytes = 0;
   // Ordering of the set: every call that uses it records `ev_last` on its stream after enqueueing, and a call on a
   // DIFFERENT stream first makes its stream wait for it.  Calls return before the work runs, so "serialised by the
   // caller" alone would not order execution.
@@ -1035,6 +1037,7 @@ static void ctx_destroy(bjj_ctx* c) {
     if (S.vb_tables) hipFree(S.vb_tables);
     if (S.slow) hipFree(S.slow);
     if (S.xy) hipFree(S.xy);
+    if (S.msm) hipFree(S.msm);
     if (S.ev_scan_in) hipEventDestroy(S.ev_scan_in);
     if (S.ev_scan_out) hipEventDestroy(S.ev_scan_out);
     if (S.scan_stream) hipStreamDestroy(S.scan_stream);
@@ -2111,6 +2114,77 @@ int bjj_sign_schnorr(bjj_ctx* c, const uint8_t* keys, const uint8_t* msgs, const
   HOST_PROLOGUE("bjj_sign_schnorr", !keys || !msgs || !nonces || !out_r || !out_s || !ok);
   PipeSpec sp = {3, 3, {keys, msgs, nonces}, {32, 32, BJJ_SCHNORR_NONCE_BYTES}, {out_r, out_s, ok}, {64, BJJ_SCHNORR_S_BYTES, 1}, true};
   return run_pipelined(c, n, sp, [&](void** i, void** o, size_t cnt, void* st) { return bjj_sign_schnorr_dev(c, i[0], i[1], i[2], cnt, o[0], o[1], o[2], st); });
+}
+
+// ---- bjj_msm: Q = sum k_i P_i (k_msm.hip, msm.hpp) ------------------------------------------------------------------------
+// Window width c for window_bits = 0, by the number of points: index = ceil(log2 n), profiles/msm_window_sweep.txt.
+// Below ~2^16 points every c from 9 to 16 costs the same ~1.3-1.6 ms: the floor is the serial Horner chain of the last kernel (255
+// doublings on one lane, ~0.9 ms) and the launches, not the buckets.
+static const signed char kMsmAutoWindow[33] = {10, 10, 10, 10, 10, 10, 10, 10, 10, 10, 10, 10, 13, 13, 15, 15, 15, 15, 15, 15, 16, 16, 18, 18,
+                                                18, 18, 18, 18, 18, 18, 18, 18, 18};
+static int msm_window(size_t n, int window_bits) {
+  if (window_bits) return window_bits;
+  int lg = 0;
+  while (lg < 32 && ((size_t)1 << lg) < n) lg++;
+  return kMsmAutoWindow[lg];
+}
+static int msm_check(bjj_ctx* c, size_t n, int window_bits, const char* who) {
+  if (!c) return set_err(BJJ_E_INVALID, std::string(who) + ": ctx is NULL");
+  CHECK_N(n);
+  if (window_bits != 0 && (window_bits < 4 || window_bits > 20))
+    return set_err(BJJ_E_INVALID, std::string(who) + ": window_bits must be 0 (library's choice) or 4..20");
+  return BJJ_OK;
+}
+// the set's MSM block holds at least `bytes` (a growing block waits for the device, as ensure_scratch does)
+static int ensure_msm(ScratchSet* S, size_t bytes, const char* who) {
+  if (bytes <= S->msm_bytes) return BJJ_OK;
+  if (S->msm) { HIPCK(hipDeviceSynchronize()); HIPCK(hipFree(S->msm)); S->msm = nullptr; S->msm_bytes = 0; }
+  if (hipMalloc((void**)&S->msm, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    S->msm = nullptr;
+    return set_err(BJJ_E_NOMEM, std::string(who) + ": cannot allocate " + std::to_string(bytes >> 20) + " MB of MSM scratch");
+  }
+  S->msm_bytes = bytes;
+  return BJJ_OK;
+}
+int bjj_msm_dev(bjj_ctx* c, const void* d_pts, const void* d_scalars, size_t n, int window_bits, void* d_out, void* d_first_off_curve,
+                void* stream) {
+  { int rc = msm_check(c, n, window_bits, "bjj_msm_dev"); if (rc) return rc; }
+  if (n) { CHECK_PTR(d_pts, "bjj_msm_dev"); CHECK_PTR(d_scalars, "bjj_msm_dev"); }
+  CHECK_PTR(d_out, "bjj_msm_dev"); CHECK_PTR(d_first_off_curve, "bjj_msm_dev");
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  ENTER_DEVICE(c->device);
+  ScratchSet* S = pick_set(c, st);
+  const bjjk::MsmLayout L = bjjk::msm_layout(n, msm_window(n, window_bits));
+  { int rc = ensure_msm(S, L.bytes, "bjj_msm_dev"); if (rc) return rc; }
+  { int rc = set_enter(c, S, st); if (rc) return rc; }
+  LAUNCHCK(bjjk::msm(st, L, (const uint8_t*)d_pts, (const uint8_t*)d_scalars, n, S->msm, (uint8_t*)d_out, (unsigned long long*)d_first_off_curve),
+           "bjj_msm_dev");
+  return set_leave(c, S, st);
+}
+// Synchronous.  The inputs are copied once, straight from the caller's arrays (pinned or pageable) into the set's block behind the
+// pipeline's scratch; the 64-byte result and the status word come back the same way.
+int bjj_msm(bjj_ctx* c, const uint8_t* pts, const uint8_t* scalars, size_t n, int window_bits, uint8_t* out_xy, int64_t* out_first_off_curve) {
+  { int rc = msm_check(c, n, window_bits, "bjj_msm"); if (rc) return rc; }
+  if (!out_xy || !out_first_off_curve || (n && (!pts || !scalars))) return set_err(BJJ_E_INVALID, "bjj_msm: NULL buffer");
+  hipStream_t st = c->stream;
+  ENTER_DEVICE(c->device);
+  ScratchSet* S = pick_set(c, st);
+  const bjjk::MsmLayout L = bjjk::msm_layout(n, msm_window(n, window_bits));
+  const size_t o_pts = L.bytes, o_sc = o_pts + up256(n * 64);
+  { int rc = ensure_msm(S, o_sc + up256(n * 32), "bjj_msm"); if (rc) return rc; }
+  { int rc = set_enter(c, S, st); if (rc) return rc; }
+  uint8_t* blk = S->msm;
+  if (n) {
+    HIPCK(hipMemcpyAsync(blk + o_pts, pts, n * 64, hipMemcpyHostToDevice, st));
+    HIPCK(hipMemcpyAsync(blk + o_sc, scalars, n * 32, hipMemcpyHostToDevice, st));
+  }
+  LAUNCHCK(bjjk::msm(st, L, blk + o_pts, blk + o_sc, n, blk, blk + L.o_out, (unsigned long long*)(blk + L.o_status)), "bjj_msm");
+  HIPCK(hipMemcpyAsync(out_xy, blk + L.o_out, 64, hipMemcpyDeviceToHost, st));
+  HIPCK(hipMemcpyAsync(out_first_off_curve, blk + L.o_status, 8, hipMemcpyDeviceToHost, st));
+  { int rc = set_leave(c, S, st); if (rc) return rc; }
+  HIPCK(hipStreamSynchronize(st));
+  return BJJ_OK;
 }
 
 #pragma GCC visibility pop

@@ -100,5 +100,16 @@ hipError_t sign_schnorr_ct(hipStream_t st, int grid, const uint32_t* table, int 
                            const uint8_t* nonces, size_t n, uint8_t* out_r, uint8_t* out_s, uint8_t* ok);
 int occ_sign_ct();
 int occ_sign_schnorr_ct();
+// k_msm.hip: bjj_msm -- Q = sum k_i P_i (Pippenger, msm.hpp).  The scratch of one call is ONE device block laid out by msm_layout
+// (byte offsets, 256-B aligned); `status` is the caller's int64 word (-1, or the smallest index of an off-curve point), `out` 64 bytes.
+struct MsmLayout {
+  int c, W, levels;
+  uint32_t S1, G;
+  uint64_t keys, records, slices1, nb;
+  size_t o_niels, o_red, o_counts, o_cursor, o_bsum, o_total, o_status, o_out, o_rec, o_e0, o_e1, o_buckets, o_w0, o_w1, bytes;
+};
+MsmLayout msm_layout(size_t n, int c);
+hipError_t msm(hipStream_t st, const MsmLayout& L, const uint8_t* pts, const uint8_t* scalars, size_t n, uint8_t* scratch, uint8_t* out,
+               unsigned long long* status);
 
 }  // namespace bjjk

@@ -22,6 +22,9 @@
  *   bjj_proj_add         PointProjective::add(&self, q)  src/lib.rs:88-131: raw (x, y, z) in and out, any z
  *                        (what the reference's own test chains, src/lib.rs:513-516)
  *   bjj_proj_affine      PointProjective::affine(&self)  src/lib.rs:70-85  (z == 0 -> (0, 0))
+ *   bjj_msm              no single counterpart: Q = sum k_i * P_i, equal to the fold
+ *                        acc = acc.add(&P_i.mul_scalar(k_i).projective()) from (0, 1, 1), then acc.affine()
+ *                        (src/lib.rs:149-164, 88-131, 70-85) -- see the block above bjj_msm below
  *   bjj_compress_points  Point::compress(&self)      src/lib.rs:166-178
  *   bjj_decompress_points decompress_point(bb)       src/lib.rs:192-224 (+ utils.rs modinv/modsqrt)
  *   bjj_scalar_keys      PrivateKey::scalar_key()    src/lib.rs:284-302 (Blake-512, prune, >> 3)
@@ -215,6 +218,27 @@ int bjj_point_add(bjj_ctx* ctx, const uint8_t* p_xy /* n*64 */, const uint8_t* q
 int bjj_proj_add(bjj_ctx* ctx, const uint8_t* p_xyz /* n*96 */, const uint8_t* q_xyz /* n*96 */, size_t n,
                  uint8_t* out_xyz /* n*96 */);
 int bjj_proj_affine(bjj_ctx* ctx, const uint8_t* p_xyz /* n*96 */, size_t n, uint8_t* out_xy /* n*64 */);
+/* Multi-scalar multiplication (Pippenger's bucket method on the device): ONE result for the whole batch,
+ *   Q = sum_i k_i * P_i   with k_i * P_i = Point::mul_scalar (src/lib.rs:149-164) and the sum PointProjective::add
+ *   (src/lib.rs:88-131) folded from (0, 1, 1), then .affine() (src/lib.rs:70-85).
+ * Inputs: n points (64-byte records; coordinates >= r are reduced mod r) and n scalars (32-byte records, any 256-bit value).
+ * When every point is on the curve the addition law is complete (A a square, D a non-square), the group has order 8l (so
+ * k mod 8l is exact) and canonical affine coordinates are unique: out_xy is bit-identical to the left fold above in ANY
+ * order, and to bjj_mul_var_base followed by any tree of bjj_point_add.  Small-order points, the identity, duplicates and
+ * P / -P pairs are ordinary inputs.
+ *   n == 0          out_xy = the identity (0, 1), status -1.
+ *   off-curve       a point that fails A x^2 + y^2 = 1 + D x^2 y^2 makes no fold order meaningful: it is rejected as DATA --
+ *                   out_xy = (0, 0) (not a curve point, so never a result) and the status word = the SMALLEST offending
+ *                   index; otherwise the status word is -1.  The return code stays 0 and nothing carries over to the next call.
+ *   window_bits     0 = the library picks the bucket width c from n; 4..20 forces c (tests, tuning);
+ *                   anything else is BJJ_E_INVALID.
+ * Scratch: about n * (160 + 8 ceil(255 / c)) bytes plus 160 * ceil(255 / c) * 2^(c-1) (bytes per bucket); BJJ_E_NOMEM when the
+ * device cannot provide it.  The host form is synchronous and copies the caller's arrays (pinned or pageable, identical
+ * results) once to the device; the _dev form follows the *_dev contract (16-byte aligned device pointers, enqueued on
+ * `stream`, NULL = the context's stream, no synchronisation; the device writes the int64 status word; one scratch set per
+ * stream, so two calls on two streams run at once). */
+int bjj_msm(bjj_ctx* ctx, const uint8_t* pts_xy /* n*64 */, const uint8_t* scalars /* n*32 */, size_t n,
+            int window_bits, uint8_t* out_xy /* 64 */, int64_t* out_first_off_curve);
 /* Wire format (src/lib.rs:166-178): 32 bytes = y little-endian, bit 255 = (x > (r-1)/2). */
 int bjj_compress_points(bjj_ctx* ctx, const uint8_t* pts_xy /* n*64 */, size_t n, uint8_t* out /* n*32 */);
 /* B8.mul_scalar(n).compress() in one pass: byte-identical to bjj_compress_points(bjj_mul_fixed_base(..)), half the bytes
@@ -277,6 +301,8 @@ int bjj_point_add_dev(bjj_ctx* ctx, const void* d_p_xy, const void* d_q_xy, size
                       void* stream);
 int bjj_proj_add_dev(bjj_ctx* ctx, const void* d_p_xyz, const void* d_q_xyz, size_t n, void* d_out_xyz, void* stream);
 int bjj_proj_affine_dev(bjj_ctx* ctx, const void* d_p_xyz, size_t n, void* d_out_xy, void* stream);
+int bjj_msm_dev(bjj_ctx* ctx, const void* d_pts_xy, const void* d_scalars, size_t n, int window_bits,
+                void* d_out_xy /* 64 B */, void* d_first_off_curve /* one int64 */, void* stream);
 int bjj_scalar_keys_dev(bjj_ctx* ctx, const void* d_keys, size_t n, void* d_out, void* stream);
 int bjj_public_keys_dev(bjj_ctx* ctx, const void* d_keys, size_t n, void* d_out_xy, void* stream);
 int bjj_sign_dev(bjj_ctx* ctx, const void* d_keys, const void* d_msgs, size_t n, void* d_out_r_xy, void* d_out_s,

@@ -346,6 +346,23 @@ pub fn mul_scalar_batch(points: &[Point], scalars: &[BigInt]) -> Vec<Point> {
     })
 }
 
+/// `sum points[i].mul_scalar(&scalars[i])` in one call (bjj_msm, Pippenger on the GPU): equal to the fold
+/// `acc = acc.add(&p.mul_scalar(k).projective())` from (0, 1, 1), then `acc.affine()` (lib.rs:149-164, 88-131, 70-85).
+/// Scalars are taken as |k| mod 8l on the host (mul_scalar drops the sign, lib.rs:156; exact for on-curve points, whose order
+/// divides 8l); a point off the curve is an Err.
+pub fn msm(points: &[Point], scalars: &[BigInt]) -> Result<Point, String> {
+    if points.len() != scalars.len() {
+        return Err("msm: points and scalars differ in length".into());
+    }
+    let mut pts = Vec::with_capacity(points.len() * 64);
+    let mut sc = Vec::with_capacity(scalars.len() * 32);
+    for (p, k) in points.iter().zip(scalars.iter()) {
+        pts.extend_from_slice(&point_bytes(p));
+        sc.extend_from_slice(&bigint_to_le(&b8_scalar(k), 32));   // |k| mod 8l fits the 32-byte record
+    }
+    with_gpu(|gpu| gpu.msm(&pts, &sc)).map(|b| point_from_bytes(&b))
+}
+
 /// `B8.mul_scalar(&n)` for every n (the engine of `PrivateKey::public`, lib.rs:304-306)
 pub fn mul_fixed_base_batch(scalars: &[BigInt]) -> Vec<Point> {
     let n = scalars.len();

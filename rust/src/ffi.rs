@@ -79,6 +79,7 @@ extern "C" {
     pub fn bjj_point_add(ctx: *mut BjjCtx, p_xy: *const u8, q_xy: *const u8, n: usize, out_xy: *mut u8) -> c_int;
     pub fn bjj_proj_add(ctx: *mut BjjCtx, p_xyz: *const u8, q_xyz: *const u8, n: usize, out_xyz: *mut u8) -> c_int;
     pub fn bjj_proj_affine(ctx: *mut BjjCtx, p_xyz: *const u8, n: usize, out_xy: *mut u8) -> c_int;
+    pub fn bjj_msm(ctx: *mut BjjCtx, pts_xy: *const u8, scalars: *const u8, n: usize, window_bits: c_int, out_xy: *mut u8, out_first_off_curve: *mut i64) -> c_int;
     pub fn bjj_compress_points(ctx: *mut BjjCtx, pts_xy: *const u8, n: usize, out: *mut u8) -> c_int;
     pub fn bjj_mul_fixed_base_compressed(ctx: *mut BjjCtx, scalars: *const u8, n: usize, out: *mut u8) -> c_int;
     pub fn bjj_decompress_points(ctx: *mut BjjCtx, input: *const u8, n: usize, out_xy: *mut u8, ok: *mut u8) -> c_int;
@@ -99,6 +100,7 @@ extern "C" {
     pub fn bjj_point_add_dev(ctx: *mut BjjCtx, d_p_xy: *const c_void, d_q_xy: *const c_void, n: usize, d_out_xy: *mut c_void, stream: *mut c_void) -> c_int;
     pub fn bjj_proj_add_dev(ctx: *mut BjjCtx, d_p_xyz: *const c_void, d_q_xyz: *const c_void, n: usize, d_out_xyz: *mut c_void, stream: *mut c_void) -> c_int;
     pub fn bjj_proj_affine_dev(ctx: *mut BjjCtx, d_p_xyz: *const c_void, n: usize, d_out_xy: *mut c_void, stream: *mut c_void) -> c_int;
+    pub fn bjj_msm_dev(ctx: *mut BjjCtx, d_pts_xy: *const c_void, d_scalars: *const c_void, n: usize, window_bits: c_int, d_out_xy: *mut c_void, d_first_off_curve: *mut c_void, stream: *mut c_void) -> c_int;
     pub fn bjj_scalar_keys_dev(ctx: *mut BjjCtx, d_keys: *const c_void, n: usize, d_out: *mut c_void, stream: *mut c_void) -> c_int;
     pub fn bjj_public_keys_dev(ctx: *mut BjjCtx, d_keys: *const c_void, n: usize, d_out_xy: *mut c_void, stream: *mut c_void) -> c_int;
     pub fn bjj_sign_dev(ctx: *mut BjjCtx, d_keys: *const c_void, d_msgs: *const c_void, n: usize, d_out_r_xy: *mut c_void, d_out_s: *mut c_void, d_ok: *mut c_void, stream: *mut c_void) -> c_int;

@@ -254,6 +254,23 @@ impl Gpu {
         Ok(out)
     }
 
+    /// `bjj_msm`: sum of `points[i].mul_scalar(scalars[i])` as one 64-byte record -- the fold of the reference's mul_scalar
+    /// (src/lib.rs:149-164) with PointProjective::add from the identity, then affine() (src/lib.rs:88-131, 70-85).  An empty
+    /// batch gives the identity (0, 1); a point off the curve is an Err naming the smallest such index.
+    pub fn msm(&self, points: &[u8], scalars: &[u8]) -> Result<[u8; 64], String> {
+        let n = records(points, 64, "points")?;
+        if scalars.len() != n * 32 {
+            return Err("msm: one 32-byte scalar per point".into());
+        }
+        let mut out = [0u8; 64];
+        let mut first: i64 = -1;
+        check(unsafe { ffi::bjj_msm(self.ctx, points.as_ptr(), scalars.as_ptr(), n, 0, out.as_mut_ptr(), &mut first) }, "bjj_msm")?;
+        if first != -1 {
+            return Err(format!("msm: point {} is not on the curve", first));
+        }
+        Ok(out)
+    }
+
     pub fn compress_points(&self, pts: &[u8]) -> Result<Vec<u8>, String> {
         let n = records(pts, 64, "points")?;
         let mut out = vec![0u8; n * 32];

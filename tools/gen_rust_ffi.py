@@ -25,7 +25,7 @@ def rust_type(ctype):
     base = t.replace("const", "").strip()
     stars = base.count("*")
     base = base.replace("*", "").strip()
-    m = {"void": "c_void", "uint8_t": "u8", "uint32_t": "u32", "uint64_t": "u64", "int": "c_int", "size_t": "usize", "char": "c_char", "double": "f64",
+    m = {"void": "c_void", "uint8_t": "u8", "uint32_t": "u32", "uint64_t": "u64", "int64_t": "i64", "int": "c_int", "size_t": "usize", "char": "c_char", "double": "f64",
          "bjj_ctx": "BjjCtx", "bjj_multi": "BjjMulti", "bjj_info": "BjjInfo"}[base]
     for _ in range(stars):
         m = ("*const " if const and _ == 0 else "*mut ") + m
