@@ -766,6 +766,14 @@ BJJ_HD void limbs_addmul(Fr& a, u32 q, const Fr& b) {  // a += q*b
     c >>= 29;
   }
 }
+// c = v*s mod l, the fixed-base scalar of the EdDSA fast path (B8 has order l), from the raw 256-bit s and (|v|, sign(v)) of
+// lattice_short_pair (|v| < 2^251): three Montgomery products mod l, each within fl_mul's bound, then l - c for negative v
+BJJ_HD Fr verify_fb_scalar(const u32 sw[8], const Fr& vmag, bool vneg, const Consts& K) {
+  Fr sl = fl_mul(fr_from_words(sw), K.L_R1, K);                                  // s mod l (< 2l)
+  Fr c = fl_canon4(fl_mul(vmag, fl_mul(sl, K.L_R2, K), K), K);                   // |v|*s mod l
+  if (vneg && !limbs_is_zero(c)) { Fr t = K.L; limbs_submul(t, 1u, c); c = t; }  // l - c
+  return c;
+}
 BJJ_HD Fr limbs_shift_up(const Fr& a, int k) {  // a * 2^(29 k), k in 0..8 (high limbs fall off: callers keep it in range)
   Fr r = a;
 #pragma unroll
@@ -939,10 +947,7 @@ BJJ_HD int verify_fast_t(const VerifyIn& in, const G& fb, int W, int nwin, u32* 
   Fr u, vmag;
   bool vneg;
   lattice_short_pair(plain_mod_l(hm_plain, K), u, vmag, vneg, K);
-  // c = v*s mod l for the fixed-base part (B8 has order l): three Montgomery products mod l
-  Fr sl = fl_mul(fr_from_words(sw), K.L_R1, K);                                  // s mod l (< 2l)
-  Fr c = fl_canon4(fl_mul(vmag, fl_mul(sl, K.L_R2, K), K), K);                   // |v|*s mod l
-  if (vneg && !limbs_is_zero(c)) { Fr t = K.L; limbs_submul(t, 1u, c); c = t; }  // l - c
+  const Fr c = verify_fb_scalar(sw, vmag, vneg, K);             // v*s mod l for the fixed-base part (B8 has order l)
   u32 cw[8];
   fr_to_words(c, cw);
   // P1 = -8A, P2 = -sign(v) R   (both on the a'=-1 curve)

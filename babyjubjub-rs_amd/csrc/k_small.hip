@@ -345,12 +345,7 @@ __global__ void __launch_bounds__(2 * BJJ_VS_BLOCK) bjj_k_eddsa_verify_small(con
   lattice_short_pair(plain_mod_l(hm_plain, c_K), u, vmag, vneg, c_K);
   u32 sw[8], cw[8];
   load_w8(sg + i * 32, sw);
-  {
-    const Fr sl = fl_mul(fr_from_words(sw), c_K.L_R1, c_K);
-    Fr c = fl_canon4(fl_mul(vmag, fl_mul(sl, c_K.L_R2, c_K), c_K), c_K);
-    if (vneg && !limbs_is_zero(c)) { Fr t = c_K.L; limbs_submul(t, 1u, c); c = t; }
-    fr_to_words(c, cw);
-  }
+  fr_to_words(verify_fb_scalar(sw, vmag, vneg, c_K), cw);
   if (role) qfb_prefetch(table, W, nwin, cw);
   // this wave's point on the a' = -1 curve, one coordinate per lane, and its table: wave 0 -8A, wave 1 -sign(v) R
   {
@@ -451,12 +446,7 @@ __global__ void __launch_bounds__(BJJ_VS_BLOCK) bjj_k_eddsa_verify_small_joint(c
   lattice_short_pair(plain_mod_l(hm_plain, c_K), u, vmag, vneg, c_K);
   u32 sw[8], cw[8];
   load_w8(sg + i * 32, sw);
-  {
-    const Fr sl = fl_mul(fr_from_words(sw), c_K.L_R1, c_K);
-    Fr c = fl_canon4(fl_mul(vmag, fl_mul(sl, c_K.L_R2, c_K), c_K), c_K);
-    if (vneg && !limbs_is_zero(c)) { Fr t = c_K.L; limbs_submul(t, 1u, c); c = t; }
-    fr_to_words(c, cw);
-  }
+  fr_to_words(verify_fb_scalar(sw, vmag, vneg, c_K), cw);
   qfb_prefetch(table, W, nwin, cw);
   // P1 = -8A, P2 = -sign(v) R on the a' = -1 curve, one coordinate per lane; their tables
   {
@@ -620,7 +610,7 @@ __device__ __forceinline__ void sign_small_body(const u32* __restrict__ table, i
 #pragma unroll
   for (int k = 0; k < 8; k++) buf[8 + k] = msg[k];               // :318-325
   blake512_words(buf, 16, dig);                                  // :326
-  const Fr r = fl_canon4(fr_add(fl_mul(limbs_from_bits(dig, 16, 0), c_K.L_R1, c_K), fl_mul(limbs_from_bits(dig, 16, 261), c_K.L_R2, c_K)), c_K);   // :327-328
+  const Fr r = digest_mod_l(dig, c_K);                           // :327-328
   u32 rw[8];
   fr_to_words(r, rw);
   const GatherPerLane fb = {table};

@@ -26,26 +26,6 @@
 // Interleaved A/B, one MI355X (profiles/r03_ab_k2_tiles.txt): alone 15.0 vs 15.4 ms (tiles +2.6 %); on two streams 72.7 vs
 // 74.1 M mults/s (strided +1.9 %).  BJJ_K2_VARIANT=0|1 forces one form.
 
-// (n >> 3) mod l of a little-endian integer of nw words, as 8 words -> n mod 8l = 8*that + (n & 7) < 2^254.
-// Horner over 261-bit chunks, most significant first: acc <- acc * 2^261 + chunk (mod l), with the mod-l Montgomery
-// products of the signer row (fl_mul(acc, 2^522) = acc * 2^261, fl_mul(chunk, 2^261) = chunk; each < 2l).
-__device__ void wide_scalar_mod_order(const u32* __restrict__ w, int nw, u32 out[8]) {
-  const int bits = nw * 32 - 3;
-  const int chunks = (bits + 260) / 261;
-  Fr acc = fr_zero();
-#pragma unroll 1
-  for (int c = chunks - 1; c >= 0; c--) {
-    Fr hi = fl_mul(acc, c_K.L_R2, c_K);
-    Fr lo = fl_mul(limbs_from_bits(w, nw, 3 + 261 * c), c_K.L_R1, c_K);
-    acc = fl_canon4(fr_add(hi, lo), c_K);
-  }
-  u32 q[8];
-  fr_to_words(acc, q);   // < l < 2^251
-  out[0] = (q[0] << 3) | (w[0] & 7u);
-#pragma unroll
-  for (int i = 1; i < 8; i++) out[i] = (q[i] << 3) | (q[i - 1] >> 29);
-}
-
 // ---------------------------------------------------------------------------
 // K2: variable base.  An off-curve point (the reference's Point has pub fields and no check, src/lib.rs:134-138) is not this
 // kernel's item: K6 (bjj_k_mul_var_base_exact) replays the reference's loop for it and owns its output slot, which K2 never
@@ -76,7 +56,7 @@ __device__ __forceinline__ void var_base_body(const uint8_t* __restrict__ pts, c
     if (ref_on_curve(x, y, c_K)) {
       Ext p;
       if (WIDE) {
-        wide_scalar_mod_order((const u32*)(scalars + i * (size_t)sc_words * 4), sc_words, sc);
+        wide_scalar_mod_order((const u32*)(scalars + i * (size_t)sc_words * 4), sc_words, sc, c_K);
         Ext P = ext_from_ref_affine(x, y, c_K);
         vb_build_table(P, tbl, c_K, true);
         p = vb_mul_windowed(tbl, sc, 64, c_K);

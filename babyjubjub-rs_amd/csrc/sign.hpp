@@ -86,6 +86,34 @@ BJJ_HD Fr limbs_from_bits(const u32* w, int nw, int lo) {
   return r;
 }
 // ---------------------------------------------------------------------------
+// Reductions mod l / 8l of wide integers, with the Montgomery products mod l of bjj_device.hpp (fl_mul: a*b*2^-261, result
+// < 2l when a*b < l*2^261).  fl_mul(X, 2^261 mod l) = X mod l and fl_mul(X, 2^522 mod l) = X*2^261 mod l, each < 2l for
+// X < 2^261, so a sum of two such terms is < 4l and fl_canon4 makes it canonical.
+// ---------------------------------------------------------------------------
+// from_bytes_le(64-byte Blake-512 digest) mod l (src/lib.rs:327-328):  X = X0 + 2^261 X1
+BJJ_HD Fr digest_mod_l(const u32 dig[16], const Consts& K) {
+  return fl_canon4(fr_add(fl_mul(limbs_from_bits(dig, 16, 0), K.L_R1, K), fl_mul(limbs_from_bits(dig, 16, 261), K.L_R2, K)), K);
+}
+// (n >> 3) mod l of a little-endian integer of nw words, as 8 words -> n mod 8l = 8*that + (n & 7) < 2^254.
+// Horner over 261-bit chunks, most significant first: acc <- acc * 2^261 + chunk (mod l), with the mod-l Montgomery
+// products of the signer row (fl_mul(acc, 2^522) = acc * 2^261, fl_mul(chunk, 2^261) = chunk; each < 2l).
+BJJ_HD void wide_scalar_mod_order(const u32* __restrict__ w, int nw, u32 out[8], const Consts& K) {
+  const int bits = nw * 32 - 3;
+  const int chunks = (bits + 260) / 261;
+  Fr acc = fr_zero();
+#pragma unroll 1
+  for (int c = chunks - 1; c >= 0; c--) {
+    Fr hi = fl_mul(acc, K.L_R2, K);
+    Fr lo = fl_mul(limbs_from_bits(w, nw, 3 + 261 * c), K.L_R1, K);
+    acc = fl_canon4(fr_add(hi, lo), K);
+  }
+  u32 q[8];
+  fr_to_words(acc, q);   // < l < 2^251
+  out[0] = (q[0] << 3) | (w[0] & 7u);
+#pragma unroll
+  for (int i = 1; i < 8; i++) out[i] = (q[i] << 3) | (q[i - 1] >> 29);
+}
+// ---------------------------------------------------------------------------
 // PrivateKey::scalar_key (src/lib.rs:284-302): Blake-512(key)[..32], pruned, >> 3
 // `pruned` is the value before the shift (== scalar_key << 3, what lib.rs:335 multiplies by);
 // hi = digest words 8..15 (h[32..64], the nonce prefix of sign).
@@ -113,8 +141,7 @@ BJJ_HD bool sign_item(const u32 key[8], const u32 msg[8], const G& fb_table, int
 #pragma unroll
   for (int i = 0; i < 8; i++) buf[8 + i] = msg[i];               // :318-325  h[32..64] || msg32
   blake512_words(buf, 16, dig);                                  // :326
-  // r = from_bytes_le(digest) mod l (:327-328):  X = X0 + 2^261 X1
-  Fr r = fl_canon4(fr_add(fl_mul(limbs_from_bits(dig, 16, 0), K.L_R1, K), fl_mul(limbs_from_bits(dig, 16, 261), K.L_R2, K)), K);
+  Fr r = digest_mod_l(dig, K);                                    // r = from_bytes_le(digest) mod l (:327-328)
   u32 rw[8];
   fr_to_words(r, rw);
   Ext Rp = fixed_base_mul(fb_table, W, nwin, rw, K);             // :329
@@ -147,18 +174,21 @@ BJJ_HD bool sign_item(const u32 key[8], const u32 msg[8], const u32* fb_table, i
 // Returns false where the reference returns Err (msg > Q, :365-367).
 constexpr int SCHNORR_K_WORDS = 32;   // 1024-bit nonce
 constexpr int SCHNORR_S_WORDS = 40;   // 160-byte record of s
+// k mod l of the 1024-bit nonce (for the fixed-base engine: B8 has order l):  k = X0 + 2^261 X1 + 2^522 X2 + 2^783 X3
+BJJ_HD Fr nonce_mod_l(const u32 k[SCHNORR_K_WORDS], const Consts& K) {
+  Fr t1 = fl_mul(limbs_from_bits(k, SCHNORR_K_WORDS, 261), K.L_R2, K);
+  Fr t2 = fl_mul(fl_mul(limbs_from_bits(k, SCHNORR_K_WORDS, 522), K.L_R2, K), K.L_R2, K);
+  Fr t3 = fl_mul(fl_mul(fl_mul(limbs_from_bits(k, SCHNORR_K_WORDS, 783), K.L_R2, K), K.L_R2, K), K.L_R2, K);
+  Fr t0 = fl_mul(limbs_from_bits(k, SCHNORR_K_WORDS, 0), K.L_R1, K);
+  return fl_canon4(fr_add(fl_canon4(fr_add(t0, t1), K), fl_canon4(fr_add(t2, t3), K)), K);  // each term < 2l
+}
 template <class G>
 BJJ_HD bool sign_schnorr_item(const u32 key[8], const u32 msg[8], const u32 k[SCHNORR_K_WORDS], const G& fb_table, int W,
                               int nwin, u32 out_rx[8], u32 out_ry[8], u32 out_s[SCHNORR_S_WORDS], const Consts& K) {
   const bool good = !words_gt_modulus(msg);                      // straight-line: see sign_item
   u32 sk[8], pruned[8], hi[8];
   scalar_key_words(key, sk, pruned, hi);                         // :358 (and :354 through public())
-  // k mod l for the fixed-base engine (B8 has order l):  k = X0 + 2^261 X1 + 2^522 X2 + 2^783 X3
-  Fr t1 = fl_mul(limbs_from_bits(k, SCHNORR_K_WORDS, 261), K.L_R2, K);
-  Fr t2 = fl_mul(fl_mul(limbs_from_bits(k, SCHNORR_K_WORDS, 522), K.L_R2, K), K.L_R2, K);
-  Fr t3 = fl_mul(fl_mul(fl_mul(limbs_from_bits(k, SCHNORR_K_WORDS, 783), K.L_R2, K), K.L_R2, K), K.L_R2, K);
-  Fr t0 = fl_mul(limbs_from_bits(k, SCHNORR_K_WORDS, 0), K.L_R1, K);
-  Fr kr = fl_canon4(fr_add(fl_canon4(fr_add(t0, t1), K), fl_canon4(fr_add(t2, t3), K)), K);  // each term < 2l
+  Fr kr = nonce_mod_l(k, K);                                     // k mod l for the fixed-base engine (B8 has order l)
   u32 kw[8];
   fr_to_words(kr, kw);
   Ext Rp = fixed_base_mul(fb_table, W, nwin, kw, K);             // :351

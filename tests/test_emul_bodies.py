@@ -5,6 +5,7 @@ C ABI); it exists so arithmetic-contract violations are caught where there is no
 import ctypes
 
 from conftest import le32, pack, unpack
+from scalar_ref import pair_bits
 
 
 def hexint(x):
@@ -150,20 +151,6 @@ def test_emul_verify_half_size_scalar_boundaries(emul, oracle, pyoracle):
         v = -v if neg else v
         assert (u - v * k) % L == 0 and v % 2 == 1 and v % L != 0, k
 
-    def pair_bits(kappa):  # independent restatement of the selection rule
-        r0, t0, r1, t1 = L, 0, kappa, 1
-        while r1 >= (1 << 126):
-            q = r0 // r1
-            r0, r1, t0, t1 = r1, r0 - q * r1, t1, t0 - q * t1
-        if t1 % 2:
-            return max(r1.bit_length(), abs(t1).bit_length())
-        best = max(r0.bit_length(), abs(t0).bit_length())
-        q = r0 // r1
-        r2, t2 = r0 - q * r1, t0 - q * t1
-        if r2:
-            best = min(best, max(r2.bit_length(), abs(t2).bit_length()))
-        return best
-
     n = 6000
     kk = [v % L for v in w.to_ints(w.random_u256(w.SEED_KEYS ^ 0xB0, n))]
     rho = [v % L for v in w.to_ints(w.random_u256(w.SEED_NONCES ^ 0xB0, n))]
@@ -184,3 +171,27 @@ def test_emul_verify_half_size_scalar_boundaries(emul, oracle, pyoracle):
             got = emul.emul_verify(A[i].tobytes(), R[i].tobytes(), le32(s), msg[i].tobytes(), 6)
             want = oracle.verify(A[i], R[i], np.frombuffer(le32(s), np.uint8), msg[i])[0]
             assert got == want == (1 if s == S else 0), (i, pair_bits(hm[i] % L))
+
+
+def test_emul_scalar_arithmetic_edges(emul):
+    """The scalar arithmetic (scalar_mod_l, scalar_mod_order, plain_mod_l, fl_mul / fl_canon4, the signers' digest and nonce
+    reductions, wide_scalar_mod_order at every admitted word count, verify's c = v*s mod l, lattice_short_pair and
+    euclid_partial_step) through the ops of tests/devfuzz/scalar_ops.hpp on the g++ build, against Python integers: every
+    edge set of tests/scalar_ref.py and a few thousand seeded random inputs per op.  tests/test_gpu_scalar_fuzz.py runs the
+    same ops on the device."""
+    import random
+    import scalar_ref as sr
+    rnd = random.Random(0x5CA1E)
+    sets = sr.edge_sets()
+    outcomes = {sr.pair_outcome(k) for k in sets["short_pair"]}
+    assert outcomes == {"odd", "prev", "next", "degenerate"}, outcomes
+    for op, items in sets.items():
+        items = items + sr.random_set(op, rnd, 2000)
+        a, b = sr.records(op, items)
+        bad = sr.check(op, items, sr.cpu_run(emul, op, a, b))
+        assert bad == [], (op, len(bad), bad[:3])
+    for nw in sr.WIDE_WORD_COUNTS[::9] + [1024]:
+        items = sr.edges_wide(nw) + sr.random_set("wide", rnd, 20, nw)
+        a, _ = sr.records("wide", items, nw)
+        bad = sr.check("wide", items, sr.cpu_run(emul, "wide", a, None, nw))
+        assert bad == [], (nw, len(bad), bad[:3])
