@@ -20,6 +20,9 @@ BJJ_WINDOW_AUTO = -1
 BJJ_MAX_SCALAR_BYTES = 4096
 BJJ_TRANSPORT_RCCL = 0
 BJJ_TRANSPORT_PEER_COPY = 1
+BJJ_TABLE_ALLOC_PLAIN = 0
+BJJ_TABLE_ALLOC_UNCACHED = 1
+BJJ_TABLE_ALLOC_UNCACHED_FELL_BACK = 2
 
 # every symbol include/bjj_hip.h declares
 EXPORTED_SYMBOLS = (
@@ -73,6 +76,7 @@ class BjjInfo(ctypes.Structure):
         ("last_host_zero_copy", ctypes.c_uint32),
         ("last_poseidon_form", ctypes.c_int),
         ("last_sign_form", ctypes.c_int),
+        ("table_alloc", ctypes.c_int),
     ]
 
 

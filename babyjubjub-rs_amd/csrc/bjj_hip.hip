@@ -162,6 +162,7 @@ struct bjj_ctx {
   u32* table = nullptr;      // [window][digit 0 .. 2^(W-1)] x 128 B
   u32* bases = nullptr;      // P_j = 2^(W j) * B8, one Niels entry per window
   size_t table_bytes = 0;
+  int table_alloc = BJJ_TABLE_ALLOC_PLAIN;   // how `table` was allocated (bjj_info.table_alloc)
   // Scratch is kept in BJJ_SCRATCH_SETS independent sets so that calls on two streams can be in flight at once
   // (pick_set): a launch whose last wave-round is only partly filled -- 2^20 verifications are 8.1 rounds of the 2 048
   // resident waves, 2^20 variable-base multiplications 5.3 rounds of the 196 608 resident lanes -- then shares the chip
@@ -1165,9 +1166,20 @@ int bjj_init(int device, int window_bits, bjj_ctx** out_ctx) {
       c->xccs = x >= 1 && x <= 16 ? x : 1;
     }
   }
+  const char* env_uncached = getenv("BJJ_TABLE_UNCACHED");   // "1" / "0"; anything else = the default (plain)
+  const bool want_uncached = env_uncached && env_uncached[0] == '1';
   for (;;) {
     c->table_bytes = fixed_stride(c->W) * (size_t)c->nwin * NIELS_WORDS * sizeof(u32);
-    se = hipMalloc((void**)&c->table, c->table_bytes);
+    // BJJ_TABLE_UNCACHED=1 (internal switch, A/B of the gather's cache behaviour): the table, and only it, as fine-grained
+    // "uncached" device memory.  The build and the check kernels access it with ordinary stores and loads either way.
+    c->table_alloc = BJJ_TABLE_ALLOC_PLAIN;
+    se = hipErrorUnknown;
+    if (want_uncached) {
+      se = hipExtMallocWithFlags((void**)&c->table, c->table_bytes, hipDeviceMallocUncached);
+      if (se == hipSuccess) c->table_alloc = BJJ_TABLE_ALLOC_UNCACHED;
+      else { (void)hipGetLastError(); c->table = nullptr; c->table_alloc = BJJ_TABLE_ALLOC_UNCACHED_FELL_BACK; }
+    }
+    if (se != hipSuccess) se = hipMalloc((void**)&c->table, c->table_bytes);
     if (se == hipSuccess || !autow) break;
     (void)hipGetLastError();   // auto mode: the free-memory estimate was too optimistic, take the next narrower table
     int next = 0;
@@ -1327,6 +1339,7 @@ int bjj_get_info(bjj_ctx* c, bjj_info* out) {
   info->host_copy_threads = c->pool ? (int)c->pool->th.size() : 0;
   info->kernel_fixed_base_overlap = "bjj_k_mul_fixed_base_2x256";   // the forms overlapping launches get (expect_overlap)
   info->kernel_var_base_overlap = "bjj_k_mul_var_base";
+  info->table_alloc = c->table_alloc;
   const size_t fill = cap < sizeof(full) ? cap : sizeof(full);   // never past the caller's struct
   full.struct_size = (uint32_t)fill;
   memcpy(out, &full, fill);

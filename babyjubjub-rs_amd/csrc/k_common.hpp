@@ -165,6 +165,16 @@ __device__ __forceinline__ void epilogue_run(Fr run, size_t n, size_t tid, size_
 // together (cross-lane reads).  NBUF = 2 staging areas per wave let two gathers be in flight (the start of a fresh
 // multiplication in K1); with NBUF = 1 the loops still overlap gather j+1 with addition j, whose entry is in registers by then.
 #define FB_STAGE_WORDS (64 * NIELS_WORDS)   // 8 KB: one staged entry per lane
+// Cache policy of the gather's LDS-DMA loads: the cache-policy immediate of the builtin (gfx940+: sc0 = 1, nt = 2, sc1 = 16).
+// A table line is read once per launch by construction.  K1 (NBUF = 2) loads it non-temporal: +1.4 ... 2.2 % on two streams, all
+// of it sustained clock under the power cap; sc1 / sc0 sc1 add nothing (profiles/r07_ab_k1_gather_policy.txt).
+// The NBUF = 1 users (verify, sign) have their own knob and keep the default policy: not measured with another one.
+#ifndef BJJ_GATHER_AUX
+#define BJJ_GATHER_AUX 2
+#endif
+#ifndef BJJ_GATHER_AUX_NBUF1
+#define BJJ_GATHER_AUX_NBUF1 0
+#endif
 template <int NBUF>
 struct GatherCoopLds {
   struct Pending {};
@@ -186,7 +196,7 @@ struct GatherCoopLds {
       const int c = (lane & 7) ^ ((e >> 1) & 7);
       __builtin_amdgcn_global_load_lds(table + (size_t)s * NIELS_WORDS + c * 4,
                                        (__attribute__((address_space(3))) void*)(wlds + (NBUF > 1 ? buf : 0) * FB_STAGE_WORDS + k * (8 * NIELS_WORDS)),
-                                       16, 0, 0);
+                                       16, 0, NBUF > 1 ? BJJ_GATHER_AUX : BJJ_GATHER_AUX_NBUF1);
     }
   }
   __device__ __forceinline__ Niels finish(Pending&, int buf) const {

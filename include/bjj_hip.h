@@ -149,6 +149,10 @@ enum {
 #define BJJ_WINDOW_AUTO (-1)        /* bjj_init: widest fixed-base table that fits in 60 % of the free HBM */
 #define BJJ_MAX_SCALAR_BYTES 4096   /* bjj_mul_var_base_wide: scalars up to 32768 bits */
 #define BJJ_MAX_DEVICES 64
+/* bjj_info.table_alloc */
+#define BJJ_TABLE_ALLOC_PLAIN 0               /* hipMalloc */
+#define BJJ_TABLE_ALLOC_UNCACHED 1            /* hipExtMallocWithFlags(hipDeviceMallocUncached) */
+#define BJJ_TABLE_ALLOC_UNCACHED_FELL_BACK 2  /* uncached was asked for and refused: hipMalloc */
 
 /* Library / build identification: "bjj-hip <version> gfx950". */
 const char* bjj_version(void);
@@ -360,6 +364,8 @@ typedef struct {
                                    bit 1: the kernels read the (pinned) input arrays themselves, no copy-in stage */
   int last_poseidon_form;      /* 0 = one hash per lane, 1 = six lanes per hash (short calls) */
   int last_sign_form;          /* bjj_sign / bjj_sign_compressed: 0 = one signature per lane, 1 = eight lanes per signature (short calls) */
+  int table_alloc;             /* the fixed-base table's memory, BJJ_TABLE_ALLOC_*: plain device memory (the default), uncached device memory
+                                  (BJJ_TABLE_UNCACHED=1 in the environment of bjj_init), or plain after the uncached allocation failed */
 } bjj_info;
 int bjj_get_info(bjj_ctx* ctx, bjj_info* info);
 
