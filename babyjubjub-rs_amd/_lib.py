@@ -46,6 +46,8 @@ EXPORTED_SYMBOLS = (
     "bjj_mul_fixed_base_compressed_dev", "bjj_public_keys_compressed_dev", "bjj_sign_compressed_dev",
     "bjj_msm", "bjj_msm_dev",
 )
+# every symbol the extension headers declare (include/bjj_hip_msm_batch.h); EXPORTED_SYMBOLS stays the mirror of bjj_hip.h
+EXT_SYMBOLS = ("bjj_msm_batch", "bjj_msm_batch_dev")
 
 
 class BjjInfo(ctypes.Structure):
@@ -178,6 +180,8 @@ def load():
     lib.bjj_sign_compressed_dev.argtypes = [vp, vp, vp, sz, vp, vp, vp]
     lib.bjj_msm.argtypes = [vp, vp, vp, sz, ci, vp, ctypes.POINTER(ctypes.c_int64)]
     lib.bjj_msm_dev.argtypes = [vp, vp, vp, sz, ci, vp, vp, vp]
+    lib.bjj_msm_batch.argtypes = [vp, vp, vp, sz, vp, sz, ci, vp, vp]
+    lib.bjj_msm_batch_dev.argtypes = [vp, vp, vp, sz, vp, sz, ci, vp, vp, vp]
     # multi-GPU
     pd = ctypes.POINTER(ctypes.c_double)
     lib.bjj_multi_init.argtypes = [ctypes.POINTER(ci), ci, ci, ctypes.POINTER(vp)]

@@ -277,6 +277,31 @@ class Context:
             raise BjjError("msm: point %d is not on the curve" % first.value)
         return out.reshape(1, 64)
 
+    def msm_batch(self, points, scalars, offsets, window_bits=0):
+        """m sums over the CSR segments [offsets[s], offsets[s + 1]) of one point / scalar array (bjj_msm_batch): returns
+        (out (m, 64) uint8, status (m,) int64).  out[s] and status[s] are what bjj_msm gives for that slice: an empty segment is
+        (0, 1) / -1, an off-curve point makes ITS segment (0, 0) with status[s] = its smallest index in `points` -- returned as
+        data, not raised.  offsets: m + 1 values, offsets[0] == 0, non-decreasing, offsets[m] == n (BjjError otherwise).
+        window_bits: 0 = the library's choice from the mean segment length, 4..20 forces the bucket width."""
+        a = _as_u8(points, 64, "points")
+        s = _as_u8(scalars, 32, "scalars")
+        n = a.size // 64
+        if s.size != n * 32:
+            raise BjjError("msm_batch: %d points but %d scalars" % (n, s.size // 32))
+        try:
+            off = np.ascontiguousarray(np.asarray(offsets, dtype=np.uint64).reshape(-1))
+        except (OverflowError, ValueError, TypeError) as e:
+            raise BjjError("msm_batch: offsets are unsigned 64-bit integers (%s)" % e)
+        if off.size < 1:
+            raise BjjError("msm_batch: offsets holds m + 1 values")
+        m = off.size - 1
+        out = np.empty(m * 64, dtype=np.uint8)
+        status = np.empty(m, dtype=np.int64)
+        self._ck(self.lib.bjj_msm_batch(self.handle, a.ctypes.data if n else None, s.ctypes.data if n else None, n, off.ctypes.data, m,
+                                        int(window_bits), out.ctypes.data if m else None, status.ctypes.data if m else None),
+                 "bjj_msm_batch")
+        return out.reshape(m, 64), status
+
     def set_signer_constant_time(self, on=True):
         """signer hardening: public_keys / sign / sign_schnorr scan a small 4-bit table instead of indexing the big one
         with secret digits -- no secret-dependent address or branch; bit-identical results, ~2x slower sign"""
@@ -407,6 +432,12 @@ class Context:
 
     def compress_points_dev(self, d_pts, n, d_out, stream=0):
         self._ck(self.lib.bjj_compress_points_dev(self.handle, d_pts, n, d_out, stream), "bjj_compress_points_dev")
+
+    def msm_batch_dev(self, d_pts, d_scalars, n, d_offsets, m, d_out, d_first_off_curve, window_bits=0, stream=0):
+        """bjj_msm_batch_dev: m 64-byte results and m int64 status words written by the device (-1, the smallest off-curve index of
+        the segment, or -2 in every word when the (m + 1) uint64 offsets break their contract)"""
+        self._ck(self.lib.bjj_msm_batch_dev(self.handle, d_pts, d_scalars, n, d_offsets, m, int(window_bits), d_out, d_first_off_curve,
+                                            stream), "bjj_msm_batch_dev")
 
     def msm_dev(self, d_pts, d_scalars, n, d_out, d_first_off_curve, window_bits=0, stream=0):
         """bjj_msm_dev: 64-byte result and the int64 status word (-1, or the smallest off-curve index) written by the device"""
@@ -783,3 +814,26 @@ def msm(points, scalars, ctx=None):
         raise BjjError("msm: scalars are 256-bit unsigned integers")
     x, y = _ints((ctx or default_context()).msm(pts, sc), 2)[0]
     return Point(x, y)
+
+
+def msm_batch(segments, ctx=None):
+    """[sum of points[i].mul_scalar(scalars[i]) for (points, scalars) in segments] as Points, in one call (bjj_msm_batch).
+    BjjError names the segment and the index inside it of an off-curve point."""
+    pts, sc, offsets = [], [], [0]
+    for t, (points, scalars) in enumerate(segments):
+        p = [(q.x, q.y) if isinstance(q, Point) else tuple(q) for q in points]
+        k = [int(v) for v in scalars]
+        if len(p) != len(k):
+            raise BjjError("msm_batch: segment %d has %d points but %d scalars" % (t, len(p), len(k)))
+        if any(v < 0 or v >> 256 for v in k):
+            raise BjjError("msm_batch: scalars are 256-bit unsigned integers (segment %d)" % t)
+        pts += p
+        sc += k
+        offsets.append(len(pts))
+    if len(offsets) == 1:
+        return []
+    out, status = (ctx or default_context()).msm_batch(pts, sc, offsets)
+    for t, st in enumerate(status):
+        if st != -1:
+            raise BjjError("msm_batch: segment %d: point %d is not on the curve" % (t, int(st) - offsets[t]))
+    return [Point(x, y) for x, y in _ints(out, 2)]

@@ -36,8 +36,10 @@
 #include <vector>
 
 #include "../../include/bjj_hip.h"
+#include "../../include/bjj_hip_msm_batch.h"
 #include "bjj_device.hpp"
 #include "bjj_launch.hpp"
+#include "msm.hpp"
 #include "copy_pool.hpp"
 
 using namespace bjj;
@@ -2195,6 +2197,94 @@ int bjj_msm(bjj_ctx* c, const uint8_t* pts, const uint8_t* scalars, size_t n, in
   LAUNCHCK(bjjk::msm(st, L, blk + o_pts, blk + o_sc, n, blk, blk + L.o_out, (unsigned long long*)(blk + L.o_status)), "bjj_msm");
   HIPCK(hipMemcpyAsync(out_xy, blk + L.o_out, 64, hipMemcpyDeviceToHost, st));
   HIPCK(hipMemcpyAsync(out_first_off_curve, blk + L.o_status, 8, hipMemcpyDeviceToHost, st));
+  { int rc = set_leave(c, S, st); if (rc) return rc; }
+  HIPCK(hipStreamSynchronize(st));
+  return BJJ_OK;
+}
+
+// ---- bjj_msm_batch: m sums over CSR segments in one launch chain (k_msm_batch.hip, include/bjj_hip_msm_batch.h) -------------------
+// Window width c for window_bits = 0, by the MEAN segment length n / m: index = ceil(log2 mean), profiles/msm_batch_window_sweep.txt
+// (n = 2^20; means 2^4 .. 2^16 measured, the entries between them interpolated, those beyond 2^16 extrapolated).  A single segment
+// is bjj_msm's own choice.  The key space m W B grows with 2^c for EVERY segment, so the widths stay far below bjj_msm's: per
+// segment the window pass costs about W B (2 + (2 c - 1) / 8) additions next to the W len of the records.
+static const signed char kMsmBatchAutoWindow[33] = {4, 4, 4, 4, 4, 4, 4, 4, 4, 6, 7, 8, 8, 8, 9, 9, 9, 10, 11, 12, 13, 14, 14, 14,
+                                                     14, 14, 14, 14, 14, 14, 14, 14, 14};
+static bool msm_batch_keys_fit(size_t m, int c) {
+  return (unsigned __int128)m * (unsigned)msm_windows(c) * msm_buckets(c) < ((unsigned __int128)1 << 31);
+}
+// 0 when no width fits the 31-bit key (more than 2^22 segments)
+static int msm_batch_window(size_t n, size_t m, int window_bits) {
+  if (window_bits) return window_bits;
+  if (m <= 1) return msm_window(n, 0);
+  const size_t mean = (n + m - 1) / m;
+  int lg = 0;
+  while (lg < 32 && ((size_t)1 << lg) < mean) lg++;
+  int c = kMsmBatchAutoWindow[lg];
+  while (c > MSM_MIN_C && !msm_batch_keys_fit(m, c)) c--;
+  return c;
+}
+// argument checks of both forms, before any allocation; *c_out: the window width of the call
+static int msm_batch_check(bjj_ctx* c, size_t n, size_t m, int window_bits, const char* who, int* c_out) {
+  { int rc = msm_check(c, n, window_bits, who); if (rc) return rc; }
+  if (m == 0) {
+    if (n) return set_err(BJJ_E_INVALID, std::string(who) + ": m == 0 requires n == 0");
+    return BJJ_OK;
+  }
+  const int w = msm_batch_window(n, m, window_bits);
+  if (!msm_batch_keys_fit(m, w))
+    return set_err(BJJ_E_INVALID, std::string(who) + ": key range: m * W * B = " + std::to_string(m) + " * " + std::to_string(msm_windows(w)) +
+                                      " * " + std::to_string(msm_buckets(w)) + " (window_bits " + std::to_string(w) +
+                                      ") must stay below 2^31; use fewer segments per call or a smaller window_bits");
+  *c_out = w;
+  return BJJ_OK;
+}
+int bjj_msm_batch_dev(bjj_ctx* c, const void* d_pts, const void* d_scalars, size_t n, const void* d_offsets, size_t m, int window_bits,
+                      void* d_out, void* d_first_off_curve, void* stream) {
+  int w = 0;
+  { int rc = msm_batch_check(c, n, m, window_bits, "bjj_msm_batch_dev", &w); if (rc) return rc; }
+  if (m == 0) return BJJ_OK;
+  if (n) { CHECK_PTR(d_pts, "bjj_msm_batch_dev"); CHECK_PTR(d_scalars, "bjj_msm_batch_dev"); }
+  CHECK_PTR(d_offsets, "bjj_msm_batch_dev"); CHECK_PTR(d_out, "bjj_msm_batch_dev"); CHECK_PTR(d_first_off_curve, "bjj_msm_batch_dev");
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  ENTER_DEVICE(c->device);
+  ScratchSet* S = pick_set(c, st);
+  const bjjk::MsmLayout L = bjjk::msm_batch_layout(n, m, w);
+  { int rc = ensure_msm(S, L.bytes, "bjj_msm_batch_dev"); if (rc) return rc; }
+  { int rc = set_enter(c, S, st); if (rc) return rc; }
+  LAUNCHCK(bjjk::msm_batch(st, L, (const uint8_t*)d_pts, (const uint8_t*)d_scalars, n, (const uint64_t*)d_offsets, m, S->msm, (uint8_t*)d_out,
+                           (unsigned long long*)d_first_off_curve),
+           "bjj_msm_batch_dev");
+  return set_leave(c, S, st);
+}
+// Synchronous.  The offsets are checked here, before anything is enqueued; inputs and offsets are copied once into the set's block.
+int bjj_msm_batch(bjj_ctx* c, const uint8_t* pts, const uint8_t* scalars, size_t n, const uint64_t* offsets, size_t m, int window_bits,
+                  uint8_t* out_xy, int64_t* out_first_off_curve) {
+  int w = 0;
+  { int rc = msm_batch_check(c, n, m, window_bits, "bjj_msm_batch", &w); if (rc) return rc; }
+  if (m == 0) return BJJ_OK;
+  if (!offsets || !out_xy || !out_first_off_curve || (n && (!pts || !scalars))) return set_err(BJJ_E_INVALID, "bjj_msm_batch: NULL buffer");
+  if (offsets[0] != 0) return set_err(BJJ_E_INVALID, "bjj_msm_batch: offsets[0] must be 0");
+  for (size_t s = 0; s < m; s++)
+    if (offsets[s] > offsets[s + 1]) return set_err(BJJ_E_INVALID, "bjj_msm_batch: offsets decrease at segment " + std::to_string(s));
+  if (offsets[m] != n) return set_err(BJJ_E_INVALID, "bjj_msm_batch: offsets[m] must equal n");
+  hipStream_t st = c->stream;
+  ENTER_DEVICE(c->device);
+  ScratchSet* S = pick_set(c, st);
+  const bjjk::MsmLayout L = bjjk::msm_batch_layout(n, m, w);
+  const size_t o_pts = L.bytes, o_sc = o_pts + up256(n * 64);
+  { int rc = ensure_msm(S, o_sc + up256(n * 32), "bjj_msm_batch"); if (rc) return rc; }
+  { int rc = set_enter(c, S, st); if (rc) return rc; }
+  uint8_t* blk = S->msm;
+  if (n) {
+    HIPCK(hipMemcpyAsync(blk + o_pts, pts, n * 64, hipMemcpyHostToDevice, st));
+    HIPCK(hipMemcpyAsync(blk + o_sc, scalars, n * 32, hipMemcpyHostToDevice, st));
+  }
+  HIPCK(hipMemcpyAsync(blk + L.o_offsets, offsets, (m + 1) * 8, hipMemcpyHostToDevice, st));
+  LAUNCHCK(bjjk::msm_batch(st, L, blk + o_pts, blk + o_sc, n, (const uint64_t*)(blk + L.o_offsets), m, blk, blk + L.o_out,
+                           (unsigned long long*)(blk + L.o_status)),
+           "bjj_msm_batch");
+  HIPCK(hipMemcpyAsync(out_xy, blk + L.o_out, m * 64, hipMemcpyDeviceToHost, st));
+  HIPCK(hipMemcpyAsync(out_first_off_curve, blk + L.o_status, m * 8, hipMemcpyDeviceToHost, st));
   { int rc = set_leave(c, S, st); if (rc) return rc; }
   HIPCK(hipStreamSynchronize(st));
   return BJJ_OK;

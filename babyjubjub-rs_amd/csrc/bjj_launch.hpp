@@ -107,9 +107,21 @@ struct MsmLayout {
   uint32_t S1, G;
   uint64_t keys, records, slices1, nb;
   size_t o_niels, o_red, o_counts, o_cursor, o_bsum, o_total, o_status, o_out, o_rec, o_e0, o_e1, o_buckets, o_w0, o_w1, bytes;
+  size_t m;               // segments (bjj_msm: 1)
+  uint64_t nwin;          // m * W: the "windows" of the key space
+  size_t o_offsets, o_flag, o_seg;   // batched form: the host form's copy of the offsets, the offsets-are-bad word, a segment word per item
 };
 MsmLayout msm_layout(size_t n, int c);
 hipError_t msm(hipStream_t st, const MsmLayout& L, const uint8_t* pts, const uint8_t* scalars, size_t n, uint8_t* scratch, uint8_t* out,
                unsigned long long* status);
+// the stages between the two key-forming passes and after them, shared with the batched form (they never look inside a key)
+hipError_t msm_scan(hipStream_t st, const MsmLayout& L, uint8_t* scratch);
+hipError_t msm_reduce(hipStream_t st, const MsmLayout& L, uint8_t* scratch, const uint32_t** wsum);
+// k_msm_batch.hip: bjj_msm_batch -- m sums over the CSR segments offsets[0 .. m] of one point / scalar array; key = (s W + j) B + |d| - 1.
+// `offsets`: m + 1 uint64 on the device; `out`: m * 64 bytes; `status`: m int64 words (-1, the smallest off-curve index of the
+// segment as a position in the whole array, or -2 everywhere when the offsets break their contract).  m >= 1.
+MsmLayout msm_batch_layout(size_t n, size_t m, int c);
+hipError_t msm_batch(hipStream_t st, const MsmLayout& L, const uint8_t* pts, const uint8_t* scalars, size_t n, const uint64_t* offsets,
+                     size_t m, uint8_t* scratch, uint8_t* out, unsigned long long* status);
 
 }  // namespace bjjk

@@ -2,45 +2,11 @@
 // No reference counterpart: the result equals the fold acc = acc.add(&P_i.mul_scalar(k_i).projective()) from (0, 1, 1), then
 // .affine() (src/lib.rs:149-164, 88-131, 70-85), for on-curve points; an off-curve point makes the call's result (0, 0) and its
 // index the status word.
-#include "k_common.hpp"
-#include "msm.hpp"
+#include "k_msm_common.hpp"
 
-#define MSM_BLOCK 256
 #define MSM_SCAN_PER_THREAD 16
 #define MSM_SCAN_TILE (MSM_BLOCK * MSM_SCAN_PER_THREAD)
 #define MSM_TOP_BLOCK 1024
-
-// ---- wave-aggregated counters ------------------------------------------------------------------------------------------------
-// arr[key] += 1 for every active lane, returning the lane's old value.  The caller controls the scalars, so a whole wave may name
-// ONE key (all scalars equal, every digit in one bucket), and even random scalars give the top window only a handful of values
-// when c does not divide 255 evenly: each round serves the lanes that share the first pending lane's key with ONE atomic (rank by
-// popcount), and the rounds go on while they serve at least 4 lanes; the rest (distinct keys) take one atomic each.  Same-address
-// atomics of a wave would otherwise queue at one L2 channel (2^20 items, c = 14: 3.3 ms for the histogram alone).  All 64 lanes of
-// the wave call this together.
-template <typename T>
-__device__ __forceinline__ T wave_counter_add(T* arr, u32 key, bool active) {
-  const int lane = (int)(threadIdx.x & 63);
-  const u64 below = (1ull << lane) - 1ull;
-  bool pending = active;
-  T pos = 0;
-#pragma unroll 1
-  for (int round = 0; round < 64; round++) {
-    const u64 m = __ballot(pending);
-    if (m == 0) break;
-    const int leader = __ffsll((long long)m) - 1;
-    const u32 lkey = (u32)__shfl((int)key, leader, 64);
-    const bool mine = pending && key == lkey;
-    const u64 grp = __ballot(mine);
-    T base = 0;
-    if (lane == leader) base = atomicAdd(&arr[lkey], (T)__popcll(grp));
-    u64 b64 = (u64)base;
-    const u32 lo = (u32)__shfl((int)(u32)b64, leader, 64), hi = (u32)__shfl((int)(u32)(b64 >> 32), leader, 64);
-    if (mine) { pos = (T)((((u64)hi << 32) | lo) + (u64)__popcll(grp & below)); pending = false; }
-    if (__popcll(grp) < 4) break;
-  }
-  if (pending) pos = atomicAdd(&arr[key], (T)1);
-  return pos;
-}
 
 // ---- 1. prepare: on-curve check, Niels points, reduced scalars, histogram -----------------------------------------------------
 __global__ void __launch_bounds__(MSM_BLOCK) bjj_k_msm_prepare(const uint8_t* __restrict__ pts, const uint8_t* __restrict__ scalars, size_t n,
@@ -193,10 +159,12 @@ static u32 slice_records(u64 records) {
   while (S < 64 && records / S > ((u64)1 << 18)) S <<= 1;
   return S;
 }
-MsmLayout msm_layout(size_t n, int c) {
+// one layout for both forms: m segments (bjj_msm: 1) share the item arrays; every per-window array holds m W windows
+static MsmLayout layout(size_t n, size_t m, int c) {
   MsmLayout L = {};
   L.c = c; L.W = msm_windows(c);
-  const u64 B = msm_buckets(c), M = (u64)L.W * B;
+  L.m = m; L.nwin = (u64)m * L.W;
+  const u64 B = msm_buckets(c), M = L.nwin * B;
   L.keys = M;
   L.records = (u64)n * L.W;
   L.S1 = slice_records(L.records);
@@ -213,46 +181,46 @@ MsmLayout msm_layout(size_t n, int c) {
   L.nb = msm_div_up(M, MSM_SCAN_TILE);
   L.o_bsum = take(L.nb * 8);
   L.o_total = take(8);
-  L.o_status = take(8);
-  L.o_out = take(64);
+  L.o_status = take(m * 8);
+  L.o_out = take(m * 64);
   L.o_rec = take(L.records * 8);
   L.o_e0 = take(len2 * MSM_ENTRY_WORDS * 4);
   L.o_e1 = take(2 * slices2 * MSM_ENTRY_WORDS * 4);
   L.o_buckets = take(M * MSM_ENTRY_WORDS * 4);
-  L.o_w0 = take((u64)L.W * L.G * MSM_ENTRY_WORDS * 4);
-  L.o_w1 = take((u64)L.W * msm_div_up(L.G, MSM_GROUP) * MSM_ENTRY_WORDS * 4);
+  L.o_w0 = take(L.nwin * L.G * MSM_ENTRY_WORDS * 4);
+  L.o_w1 = take(L.nwin * msm_div_up(L.G, MSM_GROUP) * MSM_ENTRY_WORDS * 4);
+  L.o_offsets = take((m + 1) * 8);
+  L.o_flag = take(8);
+  L.o_seg = take(n * 4);
   L.bytes = off;
   return L;
 }
+MsmLayout msm_layout(size_t n, int c) { return layout(n, 1, c); }
+MsmLayout msm_batch_layout(size_t n, size_t m, int c) { return layout(n, m ? m : 1, c); }
+
 #define MSM_CK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return e_; } while (0)
-hipError_t msm(hipStream_t st, const MsmLayout& L, const uint8_t* pts, const uint8_t* scalars, size_t n, uint8_t* scratch, uint8_t* out,
-               unsigned long long* status) {
-  u32* niels = (u32*)(scratch + L.o_niels);
-  u32* red = (u32*)(scratch + L.o_red);
+// 2. the histogram in `counts` -> scatter cursors and the record total
+hipError_t msm_scan(hipStream_t st, const MsmLayout& L, uint8_t* scratch) {
   u32* counts = (u32*)(scratch + L.o_counts);
   u64* cursor = (u64*)(scratch + L.o_cursor);
   u64* bsum = (u64*)(scratch + L.o_bsum);
   u64* total = (u64*)(scratch + L.o_total);
-  u64* rec = (u64*)(scratch + L.o_rec);
-  u32* e[2] = {(u32*)(scratch + L.o_e0), (u32*)(scratch + L.o_e1)};
-  u32* buckets = (u32*)(scratch + L.o_buckets);
-  u32* w[2] = {(u32*)(scratch + L.o_w0), (u32*)(scratch + L.o_w1)};
-  MSM_CK(hipMemsetAsync(status, 0xff, sizeof(unsigned long long), st));
-  if (n == 0) {   // the identity (0, 1): Horner over no windows
-    BJJ_LAUNCH(bjj_k_msm_finish, dim3(1), dim3(64), 0, st, (const u32*)w[0], 0, L.c, (const unsigned long long*)status, out);
-    return hipGetLastError();
-  }
-  MSM_CK(hipMemsetAsync(counts, 0, L.keys * 4, st));
-  BJJ_LAUNCH(bjj_k_msm_prepare, dim3(blocks(n)), dim3(MSM_BLOCK), 0, st, pts, scalars, n, L.c, niels, red, counts, status);
-  MSM_CK(hipGetLastError());
   BJJ_LAUNCH(bjj_k_msm_scan_tiles, dim3((unsigned)L.nb), dim3(MSM_BLOCK), 0, st, (const u32*)counts, (size_t)L.keys, bsum);
   MSM_CK(hipGetLastError());
   BJJ_LAUNCH(bjj_k_msm_scan_top, dim3(1), dim3(MSM_TOP_BLOCK), 0, st, bsum, (size_t)L.nb, total);
   MSM_CK(hipGetLastError());
   BJJ_LAUNCH(bjj_k_msm_scan_apply, dim3((unsigned)L.nb), dim3(MSM_BLOCK), 0, st, (const u32*)counts, (size_t)L.keys, (const u64*)bsum, cursor);
-  MSM_CK(hipGetLastError());
-  BJJ_LAUNCH(bjj_k_msm_scatter, dim3(blocks(n)), dim3(MSM_BLOCK), 0, st, (const u32*)red, n, L.c, cursor, rec);
-  MSM_CK(hipGetLastError());
+  return hipGetLastError();
+}
+// 4. + 5. the sorted records -> buckets -> one sum per window; *wsum: the L.nwin window sums (entry stride)
+hipError_t msm_reduce(hipStream_t st, const MsmLayout& L, uint8_t* scratch, const uint32_t** wsum) {
+  u32* niels = (u32*)(scratch + L.o_niels);
+  u32* counts = (u32*)(scratch + L.o_counts);
+  u64* total = (u64*)(scratch + L.o_total);
+  u64* rec = (u64*)(scratch + L.o_rec);
+  u32* e[2] = {(u32*)(scratch + L.o_e0), (u32*)(scratch + L.o_e1)};
+  u32* buckets = (u32*)(scratch + L.o_buckets);
+  u32* w[2] = {(u32*)(scratch + L.o_w0), (u32*)(scratch + L.o_w1)};
   BJJ_LAUNCH(bjj_k_msm_slices, dim3(blocks(L.slices1)), dim3(MSM_BLOCK), 0, st, (const u64*)rec, (const u64*)total, L.slices1, L.S1,
              (const u32*)niels, buckets, e[0]);
   MSM_CK(hipGetLastError());
@@ -263,19 +231,42 @@ hipError_t msm(hipStream_t st, const MsmLayout& L, const uint8_t* pts, const uin
     MSM_CK(hipGetLastError());
     len = 2 * ns;
   }
-  const u64 nseg = (u64)L.W * L.G;
+  const u64 nseg = L.nwin * L.G;
   BJJ_LAUNCH(bjj_k_msm_windows, dim3(blocks(nseg)), dim3(MSM_BLOCK), 0, st, (const u32*)buckets, (const u32*)counts, L.c, L.G, nseg, w[0]);
   MSM_CK(hipGetLastError());
   int cur = 0;
   for (u32 g = L.G; g > 1;) {   // G is a power of two: groups never straddle two windows
     const u32 F = g < (u32)MSM_GROUP ? g : (u32)MSM_GROUP;
     g /= F;
-    const u64 nout = (u64)L.W * g;
+    const u64 nout = L.nwin * g;
     BJJ_LAUNCH(bjj_k_msm_group, dim3(blocks(nout)), dim3(MSM_BLOCK), 0, st, (const u32*)w[cur], nout, F, w[cur ^ 1]);
     MSM_CK(hipGetLastError());
     cur ^= 1;
   }
-  BJJ_LAUNCH(bjj_k_msm_finish, dim3(1), dim3(64), 0, st, (const u32*)w[cur], L.W, L.c, (const unsigned long long*)status, out);
+  *wsum = w[cur];
+  return hipSuccess;
+}
+hipError_t msm(hipStream_t st, const MsmLayout& L, const uint8_t* pts, const uint8_t* scalars, size_t n, uint8_t* scratch, uint8_t* out,
+               unsigned long long* status) {
+  u32* niels = (u32*)(scratch + L.o_niels);
+  u32* red = (u32*)(scratch + L.o_red);
+  u32* counts = (u32*)(scratch + L.o_counts);
+  u64* cursor = (u64*)(scratch + L.o_cursor);
+  u64* rec = (u64*)(scratch + L.o_rec);
+  MSM_CK(hipMemsetAsync(status, 0xff, sizeof(unsigned long long), st));
+  if (n == 0) {   // the identity (0, 1): Horner over no windows
+    BJJ_LAUNCH(bjj_k_msm_finish, dim3(1), dim3(64), 0, st, (const u32*)(scratch + L.o_w0), 0, L.c, (const unsigned long long*)status, out);
+    return hipGetLastError();
+  }
+  MSM_CK(hipMemsetAsync(counts, 0, L.keys * 4, st));
+  BJJ_LAUNCH(bjj_k_msm_prepare, dim3(blocks(n)), dim3(MSM_BLOCK), 0, st, pts, scalars, n, L.c, niels, red, counts, status);
+  MSM_CK(hipGetLastError());
+  MSM_CK(msm_scan(st, L, scratch));
+  BJJ_LAUNCH(bjj_k_msm_scatter, dim3(blocks(n)), dim3(MSM_BLOCK), 0, st, (const u32*)red, n, L.c, cursor, rec);
+  MSM_CK(hipGetLastError());
+  const u32* wsum = nullptr;
+  MSM_CK(msm_reduce(st, L, scratch, &wsum));
+  BJJ_LAUNCH(bjj_k_msm_finish, dim3(1), dim3(64), 0, st, wsum, L.W, L.c, (const unsigned long long*)status, out);
   return hipGetLastError();
 }
 }  // namespace bjjk

@@ -227,4 +227,42 @@ BJJ_HD void msm_finish(const u32* wsum, int W, int c, bool bad, uint8_t* out, co
   store_w8(out + 32, w);
 }
 
+// ---- batched form (bjj_msm_batch, k_msm_batch.hip): m independent sums over CSR segments of one point / scalar array ----------
+// Segment s = items [offsets[s], offsets[s + 1]).  The sort key carries the segment: key = (s W + j) B + |d| - 1 < m W B, so the
+// scan, the slices, the levels, the window sums and the group sums above run unchanged with "window" s W + j; only the two
+// passes that form keys and the finish know about segments.
+// The segment of item i: the last s in [0, m - 1] with offsets[s] <= i (m >= 1).  For valid offsets that is the s with
+// offsets[s] <= i < offsets[s + 1]; for ANY content of offsets[] the loop reads only offsets[1 .. m - 1] and returns a value in
+// [0, m - 1].  Neighbouring items probe the same words (one line per step and wave almost everywhere).
+BJJ_HD u32 msm_find_segment(const u64* offsets, size_t m, u64 i) {
+  size_t lo = 0, hi = m;
+  while (hi - lo > 1) {
+    const size_t mid = lo + (hi - lo) / 2;
+    if (offsets[mid] <= i) lo = mid; else hi = mid;
+  }
+  return (u32)lo;
+}
+BJJ_HD u32 msm_batch_key(u32 s, int W, int j, u32 B, u32 b) { return (s * (u32)W + (u32)j) * B + b - 1u; }
+// condition k (k = 0 .. m) of the offsets contract: offsets[0] == 0, non-decreasing, offsets[m] == n
+BJJ_HD bool msm_offset_ok(const u64* offsets, size_t m, u64 n, size_t k) {
+  bool ok = true;
+  if (k == 0) ok = ok && offsets[0] == 0;
+  if (k == m) ok = ok && offsets[m] == n;
+  if (k < m) ok = ok && offsets[k] <= offsets[k + 1];
+  return ok;
+}
+// Segment s of the batch: Horner over its W window sums.  status: the segment's word (-1, or the smallest off-curve index of the
+// whole array inside the segment); offsets_bad: the offsets contract is broken -> every result (0, 0), every status word -2.
+BJJ_HD void msm_batch_finish(const u32* wsum, size_t s, int W, int c, unsigned long long* status, bool offsets_bad, uint8_t* out,
+                             const Consts& K) {
+  if (offsets_bad) {
+    const u32 z[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+    store_w8(out + s * 64, z);
+    store_w8(out + s * 64 + 32, z);
+    status[s] = ~1ull;   // -2
+    return;
+  }
+  msm_finish(wsum + s * (size_t)W * MSM_ENTRY_WORDS, W, c, status[s] != ~0ull, out + s * 64, K);
+}
+
 }  // namespace bjj
