@@ -88,16 +88,58 @@ struct DeviceGuard {
   DeviceGuard dg_(dev);                                                                                         \
   if (dg_.err != hipSuccess) return set_err(BJJ_E_HIP, std::string("hipSetDevice: ") + hipGetErrorString(dg_.err))
 
+static void secure_bzero(void* p, size_t n) {
+  memset(p, 0, n);
+  __asm__ __volatile__("" : : "r"(p) : "memory");   // the stores must not be elided as dead
+}
+// ---- grow-only blocks -----------------------------------------------------------------------------------------------------
+// Every device block and every pinned host block of a context is one of these: a pointer and its capacity in BYTES, owned -- the
+// destructor releases it (ctx_destroy deletes the context with its device current) and it is never copied.  grow() is the only way
+// a block gets larger: nothing happens while the request fits; otherwise the old block is freed and a new one allocated.  After a
+// failed allocation the block is EMPTY (null, capacity 0), never a dangling pointer with a stale size.  A block with `wipe` set is
+// zeroed over its whole capacity before it is freed, on growth as on release (bjj_init names the blocks key material passes through).
+enum BlockWait { NO_WAIT, WAIT_DEVICE };
+template <typename T, bool kPinned>
+struct Block {
+  T* p = nullptr;
+  size_t bytes = 0;
+  bool wipe = false;
+  Block() = default;
+  Block(const Block&) = delete;
+  Block& operator=(const Block&) = delete;
+  ~Block() { (void)release(); }
+  operator T*() const { return p; }   // a block is used where its pointer is
+  hipError_t release() {
+    if (!p) return hipSuccess;
+    if (wipe) { if (kPinned) secure_bzero(p, bytes); else (void)hipMemset(p, 0, bytes); }
+    const hipError_t e = kPinned ? hipHostFree(p) : hipFree(p);
+    p = nullptr; bytes = 0;
+    return e;
+  }
+  // WAIT_DEVICE: launches of any stream may still use the old block, so the device is waited for before it is freed (a first
+  // allocation and a request that fits wait for nothing).  NO_WAIT: nothing can be using it, or the site has waited itself.
+  hipError_t grow(size_t want, BlockWait wait = WAIT_DEVICE) {
+    if (want <= bytes) return hipSuccess;
+    if (p && wait == WAIT_DEVICE) { const hipError_t e = hipDeviceSynchronize(); if (e != hipSuccess) return e; }
+    hipError_t e = release();
+    if (e == hipSuccess) e = kPinned ? hipHostMalloc((void**)&p, want, hipHostMallocDefault) : hipMalloc((void**)&p, want);
+    if (e != hipSuccess) { p = nullptr; return e; }
+    bytes = want;
+    return hipSuccess;
+  }
+};
+template <typename T> using DevBlock = Block<T, false>;
+template <typename T> using PinBlock = Block<T, true>;
+// a list of the items that take the exact-path kernels (ScratchSet::slow, bjj_ctx::pipe_wl): [0] = count, then n item indices at most
+static size_t list_bytes(size_t n) { return (n + 16) * sizeof(u32); }
+
 #define BJJ_PIPE_BUFS 4
 #define BJJ_SCRATCH_SETS 2
 #define BJJ_STREAM_MARKS 8
 struct ScratchSet {
-  u32* scratch = nullptr;      // n * 64 B (Z, prefix)
-  size_t scratch_items = 0;
-  u32* vb_tables = nullptr;    // grid threads * VB_TABLE_WORDS * 4 B
-  size_t vb_threads = 0;
-  u32* slow = nullptr;         // [0] = count, [1..] item indices deferred to the exact-path kernels
-  size_t slow_items = 0;
+  DevBlock<u32> scratch;       // n * 64 B (Z, prefix)
+  DevBlock<u32> vb_tables;     // grid threads * VB_TABLE_WORDS_MAX * 4 B
+  DevBlock<u32> slow;          // list_bytes(n): the items deferred to the exact-path kernels
   // verify: the on-curve scan of a call is routed through this stream of the HIGHEST priority, so that while another launch
   // of the context fills the chip its few light waves get the next slots that free up instead of queueing behind that
   // launch's pending workgroups for a whole launch (profiles/r03_ab_verify_group_dispatch.txt)
@@ -107,12 +149,9 @@ struct ScratchSet {
   u32 slot_cap2 = 0;
   u32* slotq = nullptr;        // verify, one group per workgroup: per-XCD ring of free per-lane-table slots (k_verify.hip)
   u32 slot_cap = 0;            // slots per XCD
-  uint8_t* codec = nullptr;    // verify_compressed: n * (64 pk + 64 R + 32 s + 2 flags) bytes; public_keys: the scalar keys
-  size_t codec_items = 0;
-  uint8_t* xy = nullptr;       // K1 with compressed output: n * 64 B, the phase-1 stash of X, Y (the 32-byte output slot cannot hold it)
-  size_t xy_items = 0;
-  uint8_t* msm = nullptr;      // bjj_msm: one block per call laid out by bjjk::msm_layout (+ the host form's copies of the inputs)
-  size_t msm_bytes = 0;
+  DevBlock<uint8_t> codec;     // verify_compressed: n * (64 pk + 64 R + 32 s + 2 flags) bytes; public_keys: the scalar keys (wiped)
+  DevBlock<uint8_t> xy;        // K1 with compressed output: n * 64 B, the phase-1 stash of X, Y (the 32-byte output slot cannot hold it)
+  DevBlock<uint8_t> msm;       // bjj_msm: one block per call laid out by bjjk::msm_layout (+ the host form's copies of the inputs)
   // Ordering of the set: every call that uses it records `ev_last` on its stream after enqueueing, and a call on a
   // DIFFERENT stream first makes its stream wait for it.  Calls return before the work runs, so "serialised by the
   // caller" alone would not order execution.
@@ -148,22 +187,19 @@ struct bjj_ctx {
   // (BJJ_VB_SPLIT)
   int vb_split = -1;
   int occ_vb_scan = 1;
-  u32* vb_seen = nullptr;                  // [BJJ_SCRATCH_SETS] per set (device-pointer calls) + [1] the host-pointer pipeline
+  PinBlock<u32> vb_seen;                   // [BJJ_SCRATCH_SETS] per set (device-pointer calls) + [1] the host-pointer pipeline
   int last_vb_split = -1;
-  uint8_t* patch_host = nullptr;           // host-pointer pipeline: K6's results on their way into the caller's array (pinned)
-  size_t patch_host_bytes = 0;
+  PinBlock<uint8_t> patch_host;            // host-pointer pipeline: K6's results on their way into the caller's array
   int xccs = 1;                // XCDs of the device (probed at init; sizes the verify kernels' slot queues)
   int occ_decomp = 1, occ_sign = 1, occ_sign_schnorr = 1;
   // signer hardening (bjj_set_signer_constant_time): a second, small fixed-base table (4-bit windows: 63 x 9 entries) that
   // the signer kernels SCAN instead of indexing; built on first use
   bool ct_signer = false;
-  u32* ct_table = nullptr;
-  u32* ct_bases = nullptr;
+  DevBlock<u32> ct_table, ct_bases;
   int occ_sign_ct = 1, occ_sign_schnorr_ct = 1;
   hipStream_t stream = nullptr;
-  u32* table = nullptr;      // [window][digit 0 .. 2^(W-1)] x 128 B
-  u32* bases = nullptr;      // P_j = 2^(W j) * B8, one Niels entry per window
-  size_t table_bytes = 0;
+  DevBlock<u32> table;       // [window][digit 0 .. 2^(W-1)] x 128 B
+  DevBlock<u32> bases;       // P_j = 2^(W j) * B8, one Niels entry per window
   int table_alloc = BJJ_TABLE_ALLOC_PLAIN;   // how `table` was allocated (bjj_info.table_alloc)
   // Scratch is kept in BJJ_SCRATCH_SETS independent sets so that calls on two streams can be in flight at once
   // (pick_set): a launch whose last wave-round is only partly filled -- 2^20 verifications are 8.1 rounds of the 2 048
@@ -184,13 +220,10 @@ struct bjj_ctx {
   std::vector<hipEvent_t> ev_in, ev_k, ev_out;   // per chunk of a super-batch (grown on demand)
   std::vector<hipEvent_t> ev_mid;          // ... and behind a chunk's decompressions on its lane (the wire-format verifier's exact list)
   hipEvent_t ev_tail = nullptr;            // behind the exact-list stage of a call (ExactListStage::close)
-  u32* pipe_wl = nullptr;                  // ONE list of the items that take the exact kernel, per super-batch (ExactListStage)
-  size_t pipe_wl_items = 0;
-  uint8_t* dstage = nullptr;   // device staging for one super-batch: every array contiguous
-  size_t pipe_bytes = 0;
-  uint8_t* pin_in[BJJ_PIPE_BUFS] = {};     // pinned rings of the staged path (allocated on the first call that has a pageable array)
-  uint8_t* pin_out[BJJ_PIPE_BUFS] = {};
-  size_t pin_in_bytes = 0, pin_out_bytes = 0;
+  DevBlock<u32> pipe_wl;                   // ONE list of the items that take the exact kernel, per super-batch (ExactListStage)
+  DevBlock<uint8_t> dstage;                // device staging for one super-batch: every array contiguous (wiped)
+  PinBlock<uint8_t> pin_in[BJJ_PIPE_BUFS];    // pinned rings of the staged path (allocated on the first call that has a pageable array; wiped)
+  PinBlock<uint8_t> pin_out[BJJ_PIPE_BUFS];
   size_t pipe_budget = 0;                  // bytes of device staging a call may take (BJJ_PIPE_STAGING_MB)
   CopyPool* pool = nullptr;
   size_t pipe_chunk = 0, pipe_first = 0;   // chunk schedule (items): first chunk, doubling up to pipe_chunk
@@ -215,9 +248,8 @@ struct bjj_ctx {
   size_t vb_quad_max = (size_t)1 << 14;    // variable base: calls of at most this many items run four lanes per item (BJJ_VB_QUAD_MAX; 0 = never)
   int idle_alternations = 0;               // expect_overlap: consecutive alternating calls that found the other set idle
   u32 last_host_direct = 0, last_host_staged = 0, last_host_chunks = 0;
-  u32* slot_block = nullptr;               // all slot-queue rings of the context in one device allocation (slot_block_make)
-  size_t slot_block_words = 0;
-  u32* err_words = nullptr;                // pinned: the ring block as read back by ctx_check_slot_queues
+  DevBlock<u32> slot_block;                // all slot-queue rings of the context in one device allocation (slot_block_make)
+  PinBlock<u32> err_words;                 // the ring block as read back by ctx_check_slot_queues
   bool rings_used = false;                 // a kernel that pops / pushes slots has been launched since the last check
 };
 
@@ -348,22 +380,19 @@ static size_t slot_ring_words(const bjj_ctx* c, u32 cap) { return (size_t)c->xcc
 static int slot_block_make(bjj_ctx* c, u32 cap, u32 cap2) {
   if (c->slot_block) return BJJ_OK;
   const size_t per_set = slot_ring_words(c, cap) + slot_ring_words(c, cap2);
-  u32* blk = nullptr;
-  HIPCK(hipMalloc((void**)&blk, BJJ_SCRATCH_SETS * per_set * sizeof(u32)));
-  u32* host = nullptr;
-  if (hipHostMalloc((void**)&host, BJJ_SCRATCH_SETS * per_set * sizeof(u32), hipHostMallocDefault) != hipSuccess) {
-    (void)hipGetLastError(); (void)hipFree(blk);
+  HIPCK(c->slot_block.grow(BJJ_SCRATCH_SETS * per_set * sizeof(u32), NO_WAIT));
+  if (c->err_words.grow(c->slot_block.bytes, NO_WAIT) != hipSuccess) {
+    (void)hipGetLastError(); (void)c->slot_block.release();
     return set_err(BJJ_E_NOMEM, "slot queues: no pinned memory for the read-back buffer");
   }
   for (int k = 0; k < BJJ_SCRATCH_SETS; k++) {
     ScratchSet& S = c->set[k];
-    S.slotq = blk + (size_t)k * per_set;           S.slot_cap = cap;
-    S.slotq2 = S.slotq + slot_ring_words(c, cap);  S.slot_cap2 = cap2;
+    S.slotq = c->slot_block + (size_t)k * per_set;  S.slot_cap = cap;
+    S.slotq2 = S.slotq + slot_ring_words(c, cap);     S.slot_cap2 = cap2;
     int rc = slot_queue_fill(c, S.slotq, cap);
     if (!rc) rc = slot_queue_fill(c, S.slotq2, cap2);
-    if (rc) { for (ScratchSet& T : c->set) { T.slotq = T.slotq2 = nullptr; T.slot_cap = T.slot_cap2 = 0; } (void)hipFree(blk); (void)hipHostFree(host); return rc; }
+    if (rc) { for (ScratchSet& T : c->set) { T.slotq = T.slotq2 = nullptr; T.slot_cap = T.slot_cap2 = 0; } (void)c->slot_block.release(); return rc; }
   }
-  c->slot_block = blk; c->slot_block_words = BJJ_SCRATCH_SETS * per_set; c->err_words = host;
   return BJJ_OK;
 }
 // After the launches in question have completed: did a pop ever give up waiting for a slot?  ONE asynchronous copy of the ring
@@ -375,7 +404,7 @@ static int slot_block_make(bjj_ctx* c, u32 cap, u32 cap2) {
 // multi-GPU pipeline): a launch that worked on the overflow slot must never be reported as BJJ_OK.
 static int ctx_check_slot_queues(bjj_ctx* c, const char* who) {
   if (!c->slot_block || !c->rings_used) return BJJ_OK;
-  HIPCK(hipMemcpyAsync(c->err_words, c->slot_block, c->slot_block_words * sizeof(u32), hipMemcpyDeviceToHost, c->stream));
+  HIPCK(hipMemcpyAsync(c->err_words, c->slot_block, c->slot_block.bytes, hipMemcpyDeviceToHost, c->stream));
   HIPCK(hipStreamSynchronize(c->stream));
   c->rings_used = false;
   unsigned long long starved = 0;
@@ -396,16 +425,8 @@ static int ctx_check_slot_queues(bjj_ctx* c, const char* who) {
 }
 
 static int ensure_scratch(bjj_ctx* c, ScratchSet* S, size_t n) {
-  if (n > S->scratch_items) {
-    if (S->scratch) { HIPCK(hipDeviceSynchronize()); HIPCK(hipFree(S->scratch)); S->scratch = nullptr; S->scratch_items = 0; }
-    HIPCK(hipMalloc((void**)&S->scratch, n * 64));
-    S->scratch_items = n;
-  }
-  if (n > S->slow_items) {
-    if (S->slow) { HIPCK(hipDeviceSynchronize()); HIPCK(hipFree(S->slow)); S->slow = nullptr; S->slow_items = 0; }
-    HIPCK(hipMalloc((void**)&S->slow, (n + 16) * sizeof(u32)));
-    S->slow_items = n;
-  }
+  HIPCK(S->scratch.grow(n * 64));
+  HIPCK(S->slow.grow(list_bytes(n)));
   // slots of per-lane tables: K2 needs its resident lanes; verify (2 tables per lane) the waves that can be resident, rounded
   // up to a whole number per XCD (the slot queues are per XCD); plus ONE overflow slot per XCD behind the regular ones (what a
   // pop that gave up waiting continues on, k_common.hpp)
@@ -418,11 +439,7 @@ static int ensure_scratch(bjj_ctx* c, ScratchSet* S, size_t n) {
   size_t threads = tv > te ? tv : te;
   if (tv_strided > threads) threads = tv_strided;
   { int rc = slot_block_make(c, cap, cap2); if (rc) return rc; }
-  if (threads > S->vb_threads) {
-    if (S->vb_tables) { HIPCK(hipDeviceSynchronize()); HIPCK(hipFree(S->vb_tables)); S->vb_tables = nullptr; S->vb_threads = 0; }
-    HIPCK(hipMalloc((void**)&S->vb_tables, threads * VB_TABLE_WORDS_MAX * sizeof(u32)));
-    S->vb_threads = threads;
-  }
+  HIPCK(S->vb_tables.grow(threads * VB_TABLE_WORDS_MAX * sizeof(u32)));
   return BJJ_OK;
 }
 // ---------------------------------------------------------------------------
@@ -545,10 +562,6 @@ struct ExactListStage {
 };
 static size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 static size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-static void secure_bzero(void* p, size_t n) {
-  memset(p, 0, n);
-  __asm__ __volatile__("" : : "r"(p) : "memory");   // the stores must not be elided as dead
-}
 
 // ---- pinned host memory ---------------------------------------------------------------------------------------------------
 // Ranges handed out by bjj_host_alloc (hipHostMalloc) or pinned in place by bjj_host_register (hipHostRegister): process-wide,
@@ -661,25 +674,13 @@ static int ensure_pipe(bjj_ctx* c, size_t chunks, size_t dev_bytes, size_t in_ri
       HIPCK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); c->ev_mid.push_back(e);
     }
   } catch (...) { return set_err(BJJ_E_NOMEM, "host-pointer pipeline: out of host memory"); }
-  if (dev_bytes > c->pipe_bytes) {
+  if (dev_bytes > c->dstage.bytes) {   // only the lanes' kernels can still be using the staging: every call waits for its copies
     HIPCK(hipStreamSynchronize(c->stream));
     HIPCK(hipStreamSynchronize(c->stream2));
-    if (c->dstage) { HIPCK(hipFree(c->dstage)); c->dstage = nullptr; c->pipe_bytes = 0; }
-    HIPCK(hipMalloc((void**)&c->dstage, dev_bytes));
-    c->pipe_bytes = dev_bytes;
   }
-  auto grow_ring = [&](uint8_t** ring, size_t* have, size_t want) -> int {
-    if (want <= *have) return BJJ_OK;
-    for (int b = 0; b < BJJ_PIPE_BUFS; b++) {
-      if (ring[b]) { secure_bzero(ring[b], *have); HIPCK(hipHostFree(ring[b])); ring[b] = nullptr; }
-    }
-    *have = 0;
-    for (int b = 0; b < BJJ_PIPE_BUFS; b++) HIPCK(hipHostMalloc((void**)&ring[b], want, hipHostMallocDefault));
-    *have = want;
-    return BJJ_OK;
-  };
-  { int rc = grow_ring(c->pin_in, &c->pin_in_bytes, in_ring); if (rc) return rc; }
-  { int rc = grow_ring(c->pin_out, &c->pin_out_bytes, out_ring); if (rc) return rc; }
+  HIPCK(c->dstage.grow(dev_bytes, NO_WAIT));
+  for (PinBlock<uint8_t>& pin_in : c->pin_in) HIPCK(pin_in.grow(in_ring, NO_WAIT));      // nothing is in flight through the rings between calls
+  for (PinBlock<uint8_t>& pin_out : c->pin_out) HIPCK(pin_out.grow(out_ring, NO_WAIT));
   if ((in_ring || out_ring) && !c->pool) {
     int want = 4;
     if (const char* e = getenv("BJJ_STAGE_THREADS")) { const int v = atoi(e); if (v >= 1 && v <= 32) want = v; }
@@ -958,8 +959,8 @@ static int run_super_batch_body(bjj_ctx* c, size_t n, const PipeSpec& sp, const 
     if (c->dstage) hipMemsetAsync(c->dstage, 0, dev_tot, c->stream);
     const size_t slots = nchunks < (size_t)BJJ_PIPE_BUFS ? nchunks : (size_t)BJJ_PIPE_BUFS;
     for (size_t b = 0; b < slots; b++) {
-      if (c->pin_in[b] && in_ring) secure_bzero(c->pin_in[b], in_ring < c->pin_in_bytes ? in_ring : c->pin_in_bytes);
-      if (c->pin_out[b] && out_ring) secure_bzero(c->pin_out[b], out_ring < c->pin_out_bytes ? out_ring : c->pin_out_bytes);
+      if (c->pin_in[b] && in_ring) secure_bzero(c->pin_in[b], in_ring < c->pin_in[b].bytes ? in_ring : c->pin_in[b].bytes);
+      if (c->pin_out[b] && out_ring) secure_bzero(c->pin_out[b], out_ring < c->pin_out[b].bytes ? out_ring : c->pin_out[b].bytes);
     }
     hipStreamSynchronize(c->stream);
   }
@@ -1012,62 +1013,35 @@ static int run_pipelined(bjj_ctx* c, size_t n, const PipeSpec& sp, Launch launch
   }
   return rc;
 }
-static int ensure_codec(bjj_ctx* c, ScratchSet* S, size_t n) {  // 162 bytes per item of intermediate records
-  if (n > S->codec_items) {
-    if (S->codec) { HIPCK(hipDeviceSynchronize()); HIPCK(hipFree(S->codec)); S->codec = nullptr; S->codec_items = 0; }
-    HIPCK(hipMalloc((void**)&S->codec, n * 162 + 64));
-    S->codec_items = n;
-  }
+static int ensure_codec(ScratchSet* S, size_t n) {  // 162 bytes per item of intermediate records
+  HIPCK(S->codec.grow(n * 162 + 64));
   return BJJ_OK;
 }
-static int ensure_xy(bjj_ctx* c, ScratchSet* S, size_t n) {     // 64 bytes per item: X, Y of phase 1 when the output slot is 32 bytes
-  if (n > S->xy_items) {
-    if (S->xy) { HIPCK(hipDeviceSynchronize()); HIPCK(hipFree(S->xy)); S->xy = nullptr; S->xy_items = 0; }
-    HIPCK(hipMalloc((void**)&S->xy, n * 64));
-    S->xy_items = n;
-  }
+static int ensure_xy(ScratchSet* S, size_t n) {     // 64 bytes per item: X, Y of phase 1 when the output slot is 32 bytes
+  HIPCK(S->xy.grow(n * 64));
   return BJJ_OK;
 }
 static bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
+// Streams, events and the copy workers; the blocks release themselves when the context is deleted -- here, with its device current
+// and idle (the wiped ones zero themselves first: Block::wipe).
 static void ctx_destroy(bjj_ctx* c) {
   DeviceGuard dg_(c->device);
   hipDeviceSynchronize();
-  // key-derived material may sit in the codec scratch (scalar keys) and in the staging buffers: zero before release
   for (ScratchSet& S : c->set) {
-    if (S.codec) { hipMemset(S.codec, 0, S.codec_items * 162 + 64); hipFree(S.codec); }
-    if (S.scratch) hipFree(S.scratch);
-    if (S.vb_tables) hipFree(S.vb_tables);
-    if (S.slow) hipFree(S.slow);
-    if (S.xy) hipFree(S.xy);
-    if (S.msm) hipFree(S.msm);
     if (S.ev_scan_in) hipEventDestroy(S.ev_scan_in);
     if (S.ev_scan_out) hipEventDestroy(S.ev_scan_out);
     if (S.scan_stream) hipStreamDestroy(S.scan_stream);
     if (S.ev_last) hipEventDestroy(S.ev_last);
   }
   for (StreamMark& k : c->marks) if (k.ev) hipEventDestroy(k.ev);
-  if (c->table) hipFree(c->table);
-  if (c->bases) hipFree(c->bases);
-  if (c->ct_table) hipFree(c->ct_table);
-  if (c->ct_bases) hipFree(c->ct_bases);
   delete c->pool;   // joins the copy workers
   c->pool = nullptr;
-  for (int b = 0; b < BJJ_PIPE_BUFS; b++) {
-    if (c->pin_in[b]) { secure_bzero(c->pin_in[b], c->pin_in_bytes); hipHostFree(c->pin_in[b]); }
-    if (c->pin_out[b]) { secure_bzero(c->pin_out[b], c->pin_out_bytes); hipHostFree(c->pin_out[b]); }
-  }
-  if (c->dstage) { hipMemset(c->dstage, 0, c->pipe_bytes); hipFree(c->dstage); }
   for (hipEvent_t e : c->ev_in) hipEventDestroy(e);
   for (hipEvent_t e : c->ev_out) hipEventDestroy(e);
   if (c->ev_tail) hipEventDestroy(c->ev_tail);
-  if (c->pipe_wl) hipFree(c->pipe_wl);
   for (hipEvent_t e : c->ev_k) hipEventDestroy(e);
   for (hipEvent_t e : c->ev_mid) hipEventDestroy(e);
-  if (c->err_words) hipHostFree(c->err_words);
-  if (c->vb_seen) hipHostFree(c->vb_seen);
-  if (c->patch_host) hipHostFree(c->patch_host);
-  if (c->slot_block) hipFree(c->slot_block);
   if (c->s_in) hipStreamDestroy(c->s_in);
   if (c->s_out) hipStreamDestroy(c->s_out);
   if (c->stream2) hipStreamDestroy(c->stream2);
@@ -1099,6 +1073,10 @@ int bjj_init(int device, int window_bits, bjj_ctx** out_ctx) {
   if (!c) return set_err(BJJ_E_NOMEM, "bjj_init: out of host memory");
   c->device = device;
   c->cus = prop.multiProcessorCount;
+  // key-derived material passes through these blocks (scalar keys in the codec records, keys in the staging levels): zeroed before they are freed
+  c->dstage.wipe = true;
+  for (ScratchSet& S : c->set) S.codec.wipe = true;
+  for (int b = 0; b < BJJ_PIPE_BUFS; b++) c->pin_in[b].wipe = c->pin_out[b].wipe = true;
   const bool autow = window_bits == BJJ_WINDOW_AUTO;
   int W = window_bits == 0 ? BJJ_DEFAULT_WINDOW_BITS : window_bits;
   if (autow) {  // widest table that leaves 40 % of the free memory to the caller (a second context gets 26 bits)
@@ -1156,32 +1134,31 @@ int bjj_init(int device, int window_bits, bjj_ctx** out_ctx) {
   c->occ_sign = bjjk::occ_sign();
   c->occ_sign_schnorr = bjjk::occ_sign_schnorr();
   hipError_t se = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-  if (se == hipSuccess) se = hipHostMalloc((void**)&c->vb_seen, (BJJ_SCRATCH_SETS + 1) * sizeof(u32), hipHostMallocDefault);
+  if (se == hipSuccess) se = c->vb_seen.grow((BJJ_SCRATCH_SETS + 1) * sizeof(u32), NO_WAIT);
   if (se != hipSuccess) { (void)hipGetLastError(); ctx_destroy(c); return set_err(BJJ_E_HIP, std::string("bjj_init: stream/event: ") + hipGetErrorString(se)); }
-  memset(c->vb_seen, 0, (BJJ_SCRATCH_SETS + 1) * sizeof(u32));
+  memset(c->vb_seen, 0, c->vb_seen.bytes);
   { const int rc_ = ensure_pipe_streams(c); if (rc_) { ctx_destroy(c); return rc_; } }   // the hardware-queue plan of the context, fixed now
   {  // XCDs of this device (the verify kernels keep one queue of table slots per XCD)
-    u32* d_word = nullptr;
-    if (hipMalloc((void**)&d_word, sizeof(u32)) == hipSuccess) {
+    DevBlock<u32> d_word;
+    if (d_word.grow(sizeof(u32), NO_WAIT) == hipSuccess) {
       const int x = bjjk::probe_xccs(c->stream, d_word);
-      hipFree(d_word);
       c->xccs = x >= 1 && x <= 16 ? x : 1;
     }
   }
   const char* env_uncached = getenv("BJJ_TABLE_UNCACHED");   // "1" / "0"; anything else = the default (plain)
   const bool want_uncached = env_uncached && env_uncached[0] == '1';
   for (;;) {
-    c->table_bytes = fixed_stride(c->W) * (size_t)c->nwin * NIELS_WORDS * sizeof(u32);
+    const size_t table_bytes = fixed_stride(c->W) * (size_t)c->nwin * NIELS_WORDS * sizeof(u32);
     // BJJ_TABLE_UNCACHED=1 (internal switch, A/B of the gather's cache behaviour): the table, and only it, as fine-grained
     // "uncached" device memory.  The build and the check kernels access it with ordinary stores and loads either way.
     c->table_alloc = BJJ_TABLE_ALLOC_PLAIN;
     se = hipErrorUnknown;
     if (want_uncached) {
-      se = hipExtMallocWithFlags((void**)&c->table, c->table_bytes, hipDeviceMallocUncached);
-      if (se == hipSuccess) c->table_alloc = BJJ_TABLE_ALLOC_UNCACHED;
-      else { (void)hipGetLastError(); c->table = nullptr; c->table_alloc = BJJ_TABLE_ALLOC_UNCACHED_FELL_BACK; }
+      se = hipExtMallocWithFlags((void**)&c->table.p, table_bytes, hipDeviceMallocUncached);   // released with hipFree like any other
+      if (se == hipSuccess) { c->table.bytes = table_bytes; c->table_alloc = BJJ_TABLE_ALLOC_UNCACHED; }
+      else { (void)hipGetLastError(); c->table.p = nullptr; c->table_alloc = BJJ_TABLE_ALLOC_UNCACHED_FELL_BACK; }
     }
-    if (se != hipSuccess) se = hipMalloc((void**)&c->table, c->table_bytes);
+    if (se != hipSuccess) se = c->table.grow(table_bytes, NO_WAIT);
     if (se == hipSuccess || !autow) break;
     (void)hipGetLastError();   // auto mode: the free-memory estimate was too optimistic, take the next narrower table
     int next = 0;
@@ -1189,12 +1166,10 @@ int bjj_init(int device, int window_bits, bjj_ctx** out_ctx) {
     if (!next) break;
     c->W = W = next;
     c->nwin = fixed_nwin(W);
-    c->table = nullptr;
   }
-  if (se == hipSuccess) se = hipMalloc((void**)&c->bases, (size_t)c->nwin * NIELS_WORDS * sizeof(u32));
+  if (se == hipSuccess) se = c->bases.grow((size_t)c->nwin * NIELS_WORDS * sizeof(u32), NO_WAIT);
   if (se != hipSuccess) {
     (void)hipGetLastError();
-    c->table_bytes = 0;
     ctx_destroy(c);
     return set_err(BJJ_E_NOMEM, "bjj_init: cannot allocate the fixed-base table");
   }
@@ -1240,7 +1215,7 @@ static int reserve_sets(bjj_ctx* c, size_t n, int sets, bool with_codec) {
     k++;
     if (!wanted) continue;
     int rc = ensure_scratch(c, &S, n ? n : 1); if (rc) return rc;
-    if (with_codec) { rc = ensure_codec(c, &S, n ? n : 1); if (rc) return rc; }
+    if (with_codec) { rc = ensure_codec(&S, n ? n : 1); if (rc) return rc; }
   }
   return BJJ_OK;
 }
@@ -1317,11 +1292,9 @@ int bjj_get_info(bjj_ctx* c, bjj_info* out) {
   info->compute_units = c->cus;
   info->window_bits = c->W;
   info->n_windows = c->nwin;
-  info->table_bytes = c->table_bytes;
-  info->scratch_bytes = (uint64_t)c->pipe_bytes;
-  for (const ScratchSet& S : c->set)
-    info->scratch_bytes += S.scratch_items * 64 + S.vb_threads * VB_TABLE_WORDS_MAX * sizeof(u32) + S.slow_items * 4 +
-                           (S.codec_items ? S.codec_items * 162 + 64 : 0) + S.xy_items * 64;
+  info->table_bytes = c->table.bytes;
+  info->scratch_bytes = (uint64_t)c->dstage.bytes;
+  for (const ScratchSet& S : c->set) info->scratch_bytes += S.scratch.bytes + S.vb_tables.bytes + S.slow.bytes + S.codec.bytes + S.xy.bytes;
   info->kernel_fixed_base = "bjj_k_mul_fixed_base";
   info->kernel_var_base = "bjj_k_mul_var_base_tiles";   // the form a launch that runs alone gets (k_var.hip)
   info->kernel_poseidon5 = "bjj_k_poseidon5";
@@ -1351,14 +1324,13 @@ int bjj_get_info(bjj_ctx* c, bjj_info* out) {
 int bjj_check_table(bjj_ctx* c, uint64_t* n_bad) {
   if (!c || !n_bad) return set_err(BJJ_E_INVALID, "bjj_check_table: NULL argument");
   ENTER_DEVICE(c->device);
-  unsigned long long* d_bad = nullptr;
-  HIPCK(hipMalloc((void**)&d_bad, sizeof(unsigned long long)));
+  DevBlock<unsigned long long> d_bad;
+  HIPCK(d_bad.grow(sizeof(unsigned long long), NO_WAIT));
   hipError_t e = hipMemsetAsync(d_bad, 0, sizeof(unsigned long long), c->stream);
   if (e == hipSuccess) e = bjjk::check_fixed_table(c->stream, c->cus * 8, c->table, c->bases, c->W, c->nwin, d_bad);
   unsigned long long h = 0;
   if (e == hipSuccess) e = hipMemcpyAsync(&h, d_bad, sizeof(h), hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  hipFree(d_bad);
   if (e != hipSuccess) return set_err(BJJ_E_HIP, std::string("bjj_check_table: ") + hipGetErrorString(e));
   *n_bad = (uint64_t)h;
   return BJJ_OK;
@@ -1382,7 +1354,7 @@ int bjj_check_table(bjj_ctx* c, uint64_t* n_bad) {
   ENTER_DEVICE((c)->device);                                              \
   ScratchSet* S = pick_set((c), st);                                      \
   { int rc_ = ensure_scratch((c), S, (n)); if (rc_) return rc_;           \
-    if (with_codec) { rc_ = ensure_codec((c), S, (n)); if (rc_) return rc_; } \
+    if (with_codec) { rc_ = ensure_codec(S, (n)); if (rc_) return rc_; } \
     rc_ = set_enter((c), S, st); if (rc_) return rc_; }
 #define SET_LEAVE(c) return set_leave((c), S, st)
 #define LAUNCHCK_S(expr, who)                                                                       \
@@ -1421,7 +1393,7 @@ static int fixed_base_launch(bjj_ctx* c, const void* d_scalars, size_t n, void* 
     DEV_LEAVE(c);
   }
   SET_ENTER(c, stream, n, false);
-  if (compressed) { int rc_ = ensure_xy(c, S, n); if (rc_) return rc_; }
+  if (compressed) { int rc_ = ensure_xy(S, n); if (rc_) return rc_; }
   const int kv = fixed_base_variant(c, S);
   LAUNCHCK(bjjk::mul_fixed_base(st, c->cus, fixed_base_lanes(c, kv), kv, c->table, c->W, c->nwin, (const uint8_t*)d_scalars, n,
                                 (uint8_t*)d_out, S->scratch, compressed ? S->xy : nullptr), "bjj_mul_fixed_base_dev");
@@ -1544,11 +1516,7 @@ int ExactListStage::open(size_t n_, void* const* d_in, void* const* d_out, uint8
     int rc_ = ensure_scratch(c, S, 1); if (rc_) return rc_;      // the set's tables and slot queues exist
     rc_ = set_enter(c, S, S->scan_stream); if (rc_) return rc_;
   }
-  if (n > c->pipe_wl_items) {
-    if (c->pipe_wl) { HIPCK(hipDeviceSynchronize()); HIPCK(hipFree(c->pipe_wl)); c->pipe_wl = nullptr; c->pipe_wl_items = 0; }
-    HIPCK(hipMalloc((void**)&c->pipe_wl, (n + 16) * sizeof(u32)));
-    c->pipe_wl_items = n;
-  }
+  HIPCK(c->pipe_wl.grow(list_bytes(n)));
   if (kind == VAR_BASE) LAUNCHCK(bjjk::var_base_list_reset(S->scan_stream, c->pipe_wl), "variable-base list");
   else LAUNCHCK(bjjk::verify_list_reset(S->scan_stream, c->pipe_wl), "verify list");
   return BJJ_OK;
@@ -1593,12 +1561,8 @@ int ExactListStage::finish(uint8_t* host_out) {
   if (!cnt) return BJJ_OK;
   if (cnt > n) return set_err(BJJ_E_HIP, "variable base: the exact list is longer than the batch");
   const size_t need = cnt * 68;
-  if (need > c->patch_host_bytes) {
-    if (c->patch_host) { HIPCK(hipHostFree(c->patch_host)); c->patch_host = nullptr; c->patch_host_bytes = 0; }
-    const size_t want = need < ((size_t)1 << 16) ? (size_t)1 << 16 : need + need / 2;
-    HIPCK(hipHostMalloc((void**)&c->patch_host, want, hipHostMallocDefault));
-    c->patch_host_bytes = want;
-  }
+  if (need > c->patch_host.bytes)   // at least 64 KB, else half as much again as the need; the last call's copy has been waited for
+    HIPCK(c->patch_host.grow(need < ((size_t)1 << 16) ? (size_t)1 << 16 : need + need / 2, NO_WAIT));
   HIPCK(hipMemcpyAsync(c->patch_host, d_extra, cnt * 64, hipMemcpyDeviceToHost, c->s_out));
   HIPCK(hipMemcpyAsync(c->patch_host + cnt * 64, c->pipe_wl + 8, cnt * 4, hipMemcpyDeviceToHost, c->s_out));
   HIPCK(hipStreamSynchronize(c->s_out));
@@ -1872,25 +1836,21 @@ static int ensure_ct_table(bjj_ctx* c) {
   ENTER_DEVICE(c->device);
   const int nwin = fixed_nwin(BJJ_CT_W);
   const size_t bytes = fixed_stride(BJJ_CT_W) * (size_t)nwin * NIELS_WORDS * sizeof(u32);
-  u32 *t = nullptr, *b = nullptr;
-  unsigned long long* d_bad = nullptr;
+  DevBlock<unsigned long long> d_bad;
   unsigned long long bad = 1;
-  hipError_t e = hipMalloc((void**)&t, bytes);
-  if (e == hipSuccess) e = hipMalloc((void**)&b, (size_t)nwin * NIELS_WORDS * sizeof(u32));
-  if (e == hipSuccess) e = hipMalloc((void**)&d_bad, sizeof(unsigned long long));
+  hipError_t e = c->ct_table.grow(bytes, NO_WAIT);
+  if (e == hipSuccess) e = c->ct_bases.grow((size_t)nwin * NIELS_WORDS * sizeof(u32), NO_WAIT);
+  if (e == hipSuccess) e = d_bad.grow(sizeof(unsigned long long), NO_WAIT);
   if (e == hipSuccess) e = hipMemsetAsync(d_bad, 0, sizeof(unsigned long long), c->stream);
-  if (e == hipSuccess) e = bjjk::build_fixed_table(c->stream, t, b, BJJ_CT_W, nwin);
-  if (e == hipSuccess) e = bjjk::check_fixed_table(c->stream, 8, t, b, BJJ_CT_W, nwin, d_bad);   // the same induction proof as the big table
+  if (e == hipSuccess) e = bjjk::build_fixed_table(c->stream, c->ct_table, c->ct_bases, BJJ_CT_W, nwin);
+  if (e == hipSuccess) e = bjjk::check_fixed_table(c->stream, 8, c->ct_table, c->ct_bases, BJJ_CT_W, nwin, d_bad);   // the same induction proof as the big table
   if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (d_bad) hipFree(d_bad);
-  if (e != hipSuccess || bad != 0) {
-    if (t) hipFree(t);
-    if (b) hipFree(b);
+  if (e != hipSuccess || bad != 0) {   // a table that exists is a table that passed: the next call starts over
+    (void)c->ct_table.release(); (void)c->ct_bases.release();
     return e != hipSuccess ? set_err(BJJ_E_HIP, std::string("constant-time signer table: ") + hipGetErrorString(e))
                            : set_err(BJJ_E_HIP, "constant-time signer table failed its self-check");
   }
-  c->ct_table = t; c->ct_bases = b;
   c->occ_sign_ct = bjjk::occ_sign_ct();
   c->occ_sign_schnorr_ct = bjjk::occ_sign_schnorr_ct();
   return BJJ_OK;
@@ -1919,7 +1879,7 @@ static int public_keys_launch(bjj_ctx* c, const void* d_keys, size_t n, void* d_
   if (!d_keys || !d_out_xy || !aligned16(d_keys) || !aligned16(d_out_xy))
     return set_err(BJJ_E_INVALID, std::string(who) + ": NULL or not 16-byte aligned device pointer");
   SET_ENTER(c, stream, n, true);
-  if (compressed) { int rc_ = ensure_xy(c, S, n); if (rc_) return rc_; }
+  if (compressed) { int rc_ = ensure_xy(S, n); if (rc_) return rc_; }
   uint8_t* xy = compressed ? S->xy : nullptr;
   // B8.mul_scalar(&self.scalar_key()), src/lib.rs:304-306; the scalar keys live in the codec scratch only for the
   // duration of the multiplication and are wiped on the same stream right behind it
@@ -2150,17 +2110,11 @@ static int msm_check(bjj_ctx* c, size_t n, int window_bits, const char* who) {
     return set_err(BJJ_E_INVALID, std::string(who) + ": window_bits must be 0 (library's choice) or 4..20");
   return BJJ_OK;
 }
-// the set's MSM block holds at least `bytes` (a growing block waits for the device, as ensure_scratch does)
+// the set's MSM block holds at least `bytes`; a block this size may well not fit: the set stays usable, with no MSM block
 static int ensure_msm(ScratchSet* S, size_t bytes, const char* who) {
-  if (bytes <= S->msm_bytes) return BJJ_OK;
-  if (S->msm) { HIPCK(hipDeviceSynchronize()); HIPCK(hipFree(S->msm)); S->msm = nullptr; S->msm_bytes = 0; }
-  if (hipMalloc((void**)&S->msm, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    S->msm = nullptr;
-    return set_err(BJJ_E_NOMEM, std::string(who) + ": cannot allocate " + std::to_string(bytes >> 20) + " MB of MSM scratch");
-  }
-  S->msm_bytes = bytes;
-  return BJJ_OK;
+  if (S->msm.grow(bytes) == hipSuccess) return BJJ_OK;
+  (void)hipGetLastError();
+  return set_err(BJJ_E_NOMEM, std::string(who) + ": cannot allocate " + std::to_string(bytes >> 20) + " MB of MSM scratch");
 }
 int bjj_msm_dev(bjj_ctx* c, const void* d_pts, const void* d_scalars, size_t n, int window_bits, void* d_out, void* d_first_off_curve,
                 void* stream) {
@@ -2177,29 +2131,41 @@ int bjj_msm_dev(bjj_ctx* c, const void* d_pts, const void* d_scalars, size_t n, 
            "bjj_msm_dev");
   return set_leave(c, S, st);
 }
-// Synchronous.  The inputs are copied once, straight from the caller's arrays (pinned or pageable) into the set's block behind the
-// pipeline's scratch; the 64-byte result and the status word come back the same way.
-int bjj_msm(bjj_ctx* c, const uint8_t* pts, const uint8_t* scalars, size_t n, int window_bits, uint8_t* out_xy, int64_t* out_first_off_curve) {
-  { int rc = msm_check(c, n, window_bits, "bjj_msm"); if (rc) return rc; }
-  if (!out_xy || !out_first_off_curve || (n && (!pts || !scalars))) return set_err(BJJ_E_INVALID, "bjj_msm: NULL buffer");
+// The synchronous host forms of bjj_msm and bjj_msm_batch.  The inputs are copied once, straight from the caller's arrays (pinned or
+// pageable), into the set's block behind the scratch that L lays out; `results` 64-byte records and as many status words come back
+// the same way.  launch(st, blk, d_pts, d_scalars) enqueues what the form has of its own.
+extern "C++" {
+template <typename Launch>
+static int msm_host_run(bjj_ctx* c, const bjjk::MsmLayout& L, const uint8_t* pts, const uint8_t* scalars, size_t n, size_t results,
+                        uint8_t* out_xy, int64_t* out_first_off_curve, const char* who, Launch launch) {
   hipStream_t st = c->stream;
   ENTER_DEVICE(c->device);
   ScratchSet* S = pick_set(c, st);
-  const bjjk::MsmLayout L = bjjk::msm_layout(n, msm_window(n, window_bits));
   const size_t o_pts = L.bytes, o_sc = o_pts + up256(n * 64);
-  { int rc = ensure_msm(S, o_sc + up256(n * 32), "bjj_msm"); if (rc) return rc; }
+  { int rc = ensure_msm(S, o_sc + up256(n * 32), who); if (rc) return rc; }
   { int rc = set_enter(c, S, st); if (rc) return rc; }
   uint8_t* blk = S->msm;
   if (n) {
     HIPCK(hipMemcpyAsync(blk + o_pts, pts, n * 64, hipMemcpyHostToDevice, st));
     HIPCK(hipMemcpyAsync(blk + o_sc, scalars, n * 32, hipMemcpyHostToDevice, st));
   }
-  LAUNCHCK(bjjk::msm(st, L, blk + o_pts, blk + o_sc, n, blk, blk + L.o_out, (unsigned long long*)(blk + L.o_status)), "bjj_msm");
-  HIPCK(hipMemcpyAsync(out_xy, blk + L.o_out, 64, hipMemcpyDeviceToHost, st));
-  HIPCK(hipMemcpyAsync(out_first_off_curve, blk + L.o_status, 8, hipMemcpyDeviceToHost, st));
+  { int rc = launch(st, blk, blk + o_pts, blk + o_sc); if (rc) return rc; }
+  HIPCK(hipMemcpyAsync(out_xy, blk + L.o_out, results * 64, hipMemcpyDeviceToHost, st));
+  HIPCK(hipMemcpyAsync(out_first_off_curve, blk + L.o_status, results * 8, hipMemcpyDeviceToHost, st));
   { int rc = set_leave(c, S, st); if (rc) return rc; }
   HIPCK(hipStreamSynchronize(st));
   return BJJ_OK;
+}
+}  // extern "C++"
+int bjj_msm(bjj_ctx* c, const uint8_t* pts, const uint8_t* scalars, size_t n, int window_bits, uint8_t* out_xy, int64_t* out_first_off_curve) {
+  { int rc = msm_check(c, n, window_bits, "bjj_msm"); if (rc) return rc; }
+  if (!out_xy || !out_first_off_curve || (n && (!pts || !scalars))) return set_err(BJJ_E_INVALID, "bjj_msm: NULL buffer");
+  const bjjk::MsmLayout L = bjjk::msm_layout(n, msm_window(n, window_bits));
+  return msm_host_run(c, L, pts, scalars, n, 1, out_xy, out_first_off_curve, "bjj_msm",
+                      [&](hipStream_t st, uint8_t* blk, const uint8_t* d_pts, const uint8_t* d_scalars) -> int {
+    LAUNCHCK(bjjk::msm(st, L, d_pts, d_scalars, n, blk, blk + L.o_out, (unsigned long long*)(blk + L.o_status)), "bjj_msm");
+    return BJJ_OK;
+  });
 }
 
 // ---- bjj_msm_batch: m sums over CSR segments in one launch chain (k_msm_batch.hip, include/bjj_hip_msm_batch.h) -------------------
@@ -2267,27 +2233,15 @@ int bjj_msm_batch(bjj_ctx* c, const uint8_t* pts, const uint8_t* scalars, size_t
   for (size_t s = 0; s < m; s++)
     if (offsets[s] > offsets[s + 1]) return set_err(BJJ_E_INVALID, "bjj_msm_batch: offsets decrease at segment " + std::to_string(s));
   if (offsets[m] != n) return set_err(BJJ_E_INVALID, "bjj_msm_batch: offsets[m] must equal n");
-  hipStream_t st = c->stream;
-  ENTER_DEVICE(c->device);
-  ScratchSet* S = pick_set(c, st);
   const bjjk::MsmLayout L = bjjk::msm_batch_layout(n, m, w);
-  const size_t o_pts = L.bytes, o_sc = o_pts + up256(n * 64);
-  { int rc = ensure_msm(S, o_sc + up256(n * 32), "bjj_msm_batch"); if (rc) return rc; }
-  { int rc = set_enter(c, S, st); if (rc) return rc; }
-  uint8_t* blk = S->msm;
-  if (n) {
-    HIPCK(hipMemcpyAsync(blk + o_pts, pts, n * 64, hipMemcpyHostToDevice, st));
-    HIPCK(hipMemcpyAsync(blk + o_sc, scalars, n * 32, hipMemcpyHostToDevice, st));
-  }
-  HIPCK(hipMemcpyAsync(blk + L.o_offsets, offsets, (m + 1) * 8, hipMemcpyHostToDevice, st));
-  LAUNCHCK(bjjk::msm_batch(st, L, blk + o_pts, blk + o_sc, n, (const uint64_t*)(blk + L.o_offsets), m, blk, blk + L.o_out,
-                           (unsigned long long*)(blk + L.o_status)),
-           "bjj_msm_batch");
-  HIPCK(hipMemcpyAsync(out_xy, blk + L.o_out, m * 64, hipMemcpyDeviceToHost, st));
-  HIPCK(hipMemcpyAsync(out_first_off_curve, blk + L.o_status, m * 8, hipMemcpyDeviceToHost, st));
-  { int rc = set_leave(c, S, st); if (rc) return rc; }
-  HIPCK(hipStreamSynchronize(st));
-  return BJJ_OK;
+  return msm_host_run(c, L, pts, scalars, n, m, out_xy, out_first_off_curve, "bjj_msm_batch",
+                      [&](hipStream_t st, uint8_t* blk, const uint8_t* d_pts, const uint8_t* d_scalars) -> int {
+    HIPCK(hipMemcpyAsync(blk + L.o_offsets, offsets, (m + 1) * 8, hipMemcpyHostToDevice, st));
+    LAUNCHCK(bjjk::msm_batch(st, L, d_pts, d_scalars, n, (const uint64_t*)(blk + L.o_offsets), m, blk, blk + L.o_out,
+                             (unsigned long long*)(blk + L.o_status)),
+             "bjj_msm_batch");
+    return BJJ_OK;
+  });
 }
 
 #pragma GCC visibility pop
