@@ -497,4 +497,116 @@ BJJ_HD_NOINLINE Fr fr_inv_gcd(const Fr& x) {
 // 1/x in Montgomery form (0 -> 0): the low-latency binary-GCD inversion.
 BJJ_HD Fr fr_inv(const Fr& x) { return fr_inv_gcd(x); }
 
+// ---------------------------------------------------------------------------------------
+// The inversion of K1's epilogue: Bernstein-Yang division steps ("Fast constant-time gcd computation and modular
+// inversion", TCHES 2019) in batches of 29, so that the exact division by 2^29 is again a limb shift.  Same contract as
+// fr_inv_gcd (input N-form below 2r in Montgomery form, output canonical, 0 -> 0, no branch or trip count depends on the
+// operand).  What it saves over fr_inv_gcd is instructions, on the vector ALU:
+//  * a divstep needs only the low bits of (f, g) and a counter, so the inner loop runs on 32-bit registers; the binary GCD
+//    compares, subtracts, shifts and selects 60-bit approximations held in register pairs;
+//  * every masked conditional add or subtract -- of f to g, and of the matrix row (u, v) to (q, r) -- is ONE multiply-add by
+//    a factor in {0, +1, -1} (modulo 2^32; on the device the 32-bit low half of a v_mad_u64_u32) instead of xor, subtract,
+//    and, add;
+//  * f and g are signed and never made non-negative, and there is no search for the top limbs of an approximation.
+// Step bound: with the half-integer counter (delta = 1/2 at the start; here zeta = -(delta + 1/2) = -1) 590 division steps
+// bring g to 0 for every odd f and 0 <= g <= f < 2^256 (P. Wuille's convex-hull computation, github.com/sipa/safegcd-bounds,
+// the bound that libsecp256k1's modinv32 / modinv64 rely on; Bernstein and Yang's own proof gives 738 for delta = 1).
+// r < 2^254: 21 batches x 29 = 609 >= 590.
+// Invariants: d*y == f*K, e*y == g*K (mod r) with K = 2^522 (= R^2).  At the end g == 0 and f == +-1 (f == r for y == 0,
+// where d == 0), so sign(f)*d == R^2 / y, which for y = x*R is the Montgomery form of 1/x.
+// Growth of (d, e), which as in fr_inv_gcd are signed and not reduced between batches: the rows of a batch's matrix satisfy
+// |u| + |v| <= 2^29 and |q| + |r| <= 2^29, and the multiple of r that makes the division exact is below 2^29 * r, so a
+// batch grows max(|d|, |e|) by less than r: from at most r to below 22 r after 21 batches (top limb below 2^27; asserted).
+// One normalisation at the end: +32 r, then the six conditional subtractions.
+// ---------------------------------------------------------------------------------------
+BJJ_HD Fr fr_inv_k1(const Fr& x) {
+  constexpr u32 R32[NL] = {0x20u, 0x01f593f0u, 0x0b848a1fu, 0x1a121e6eu, 0x10ba5067u, 0x1b681815u, 0x14dc2822u, 0x0b84c680u, 0x060c89ceu};
+  constexpr u32 R16[NL] = {0x10u, 0x10fac9f8u, 0x05c2450fu, 0x1d090f37u, 0x185d2833u, 0x0db40c0au, 0x0a6e1411u, 0x05c26340u, 0x030644e7u};
+  constexpr u32 R8[NL] = {0x8u, 0x187d64fcu, 0x12e12287u, 0x1e84879bu, 0x0c2e9419u, 0x16da0605u, 0x05370a08u, 0x12e131a0u, 0x01832273u};
+  constexpr u32 R4[NL] = {0x4u, 0x1c3eb27eu, 0x19709143u, 0x1f4243cdu, 0x16174a0cu, 0x0b6d0302u, 0x029b8504u, 0x197098d0u, 0x00c19139u};
+  constexpr u32 R2c[NL] = {0x2u, 0x1e1f593fu, 0x1cb848a1u, 0x0fa121e6u, 0x0b0ba506u, 0x05b68181u, 0x014dc282u, 0x1cb84c68u, 0x0060c89cu};
+  constexpr u32 R1[NL] = {BJJ_N0, BJJ_N1, BJJ_N2, BJJ_N3, BJJ_N4, BJJ_N5, BJJ_N6, BJJ_N7, BJJ_N8};
+  // (f, g) and (d, e): limbs 0..7 in [0, 2^29), limb 8 a signed 32-bit top (two's complement over the whole number)
+  Fr g = fr_cond_sub_kr(x, R1);  // y, in [0, r)
+  Fr f, d = fr_zero(), e = fr_r2();
+#pragma unroll
+  for (int i = 0; i < NL; i++) f.v[i] = fr_modlimb(i);
+  u32 zeta = 0xffffffffu;  // -1
+#pragma unroll 1
+  for (int outer = 0; outer < 21; outer++) {
+    // ---- 29 division steps on the low limbs, recording 2^29 times the transition matrix (|entries| <= 2^29).
+    //      Step i reads bit 0 of g0, which depends on bits 0..i of the limbs only: 29 bits are enough.
+    u32 f0 = f.v[0], g0 = g.v[0], u = 1, v = 0, q = 0, r = 1;
+#pragma unroll
+    for (int i = 0; i < 29; i++) {
+      const u32 odd = g0 & 1u;
+      const u32 m = (u32)((int32_t)zeta >> 31) & (0u - odd);  // all ones: g odd and delta > 0 -- swap and subtract
+      const u32 sg = m | odd;                                  // g += sg * f with sg = 0 (g even), +1, or -1 (swap)
+      g0 += sg * f0; q += sg * u; r += sg * v;
+      zeta = (zeta ^ m) - 1u;
+      const u32 sw = m & 1u;                                   // swap: f <- the old g == f + the new g
+      f0 += sw * g0; u += sw * q; v += sw * r;
+      g0 >>= 1; u <<= 1; v <<= 1;
+    }
+    const int32_t mu = (int32_t)u, mv = (int32_t)v, mq = (int32_t)q, mr = (int32_t)r;
+    // ---- (f, g) <- (f u + g v, f q + g r) / 2^29   (exact; both stay signed, |.| <= max(|f|, |g|) <= r)
+    // ---- (d, e) <- (d u + e v + kd r, d q + e r + ke r) / 2^29   (exact; signed, unreduced)
+    const u32 ld = (d.v[0] * u + e.v[0] * v) & MASK29, le = (d.v[0] * q + e.v[0] * r) & MASK29;
+    const u32 kd = (ld * BJJ_NINV29) & MASK29, ke = (le * BJJ_NINV29) & MASK29;
+    Fr nf, ng, nd, ne;
+    int64_t cf = 0, cg = 0, cd = 0, ce = 0;
+#pragma unroll
+    for (int i = 0; i < NL; i++) {
+      // limbs 0..7 are below 2^29 and limb 8 is signed: every limb is a signed 32-bit factor, one v_mad_i64_i32 per product.
+      // hipcc knows that the masked limbs are non-negative and would multiply them unsigned, then mend the sign of the matrix
+      // entry with a v_mul_lo_u32 and a v_add3_u32 per product: on the device the eight products of a limb are one asm statement.
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(BJJ_NO_ASM_COLUMNS)
+      asm("v_mad_i64_i32 %0, vcc, %4, %8, %0\n\tv_mad_i64_i32 %1, vcc, %4, %10, %1\n\t"
+          "v_mad_i64_i32 %2, vcc, %6, %8, %2\n\tv_mad_i64_i32 %3, vcc, %6, %10, %3\n\t"
+          "v_mad_i64_i32 %0, vcc, %5, %9, %0\n\tv_mad_i64_i32 %1, vcc, %5, %11, %1\n\t"
+          "v_mad_i64_i32 %2, vcc, %7, %9, %2\n\tv_mad_i64_i32 %3, vcc, %7, %11, %3"
+          : "+v"(cf), "+v"(cg), "+v"(cd), "+v"(ce)
+          : "v"(f.v[i]), "v"(g.v[i]), "v"(d.v[i]), "v"(e.v[i]), "v"(mu), "v"(mv), "v"(mq), "v"(mr) : "vcc");
+#else
+      const int64_t fi = (int32_t)f.v[i], gi = (int32_t)g.v[i], di = (int32_t)d.v[i], ei = (int32_t)e.v[i];
+      cf += fi * mu + gi * mv;
+      cg += fi * mq + gi * mr;
+      cd += di * mu + ei * mv;
+      ce += di * mq + ei * mr;
+#endif
+      cd += (int64_t)((u64)kd * fr_modlimb(i));
+      ce += (int64_t)((u64)ke * fr_modlimb(i));
+      if (i > 0) {
+        nf.v[i - 1] = (u32)cf & MASK29; ng.v[i - 1] = (u32)cg & MASK29;
+        nd.v[i - 1] = (u32)cd & MASK29; ne.v[i - 1] = (u32)ce & MASK29;
+      } else {
+        BJJ_ASSERT((((u32)cf | (u32)cg | (u32)cd | (u32)ce) & MASK29) == 0);   // the divisions are exact
+      }
+      cf >>= 29; cg >>= 29; cd >>= 29; ce >>= 29;
+    }
+    nf.v[NL - 1] = (u32)(int32_t)cf; ng.v[NL - 1] = (u32)(int32_t)cg;
+    nd.v[NL - 1] = (u32)(int32_t)cd; ne.v[NL - 1] = (u32)(int32_t)ce;
+    BJJ_ASSERT(cf > -(1 << 22) && cf < (1 << 22) && cg > -(1 << 22) && cg < (1 << 22));   // |f|, |g| <= r < 2^254
+    BJJ_ASSERT(cd > -(1 << 27) && cd < (1 << 27) && ce > -(1 << 27) && ce < (1 << 27));   // |d|, |e| < 22 r < 2^259
+    f = nf; g = ng; d = nd; e = ne;
+  }
+  BJJ_ASSERT((g.v[0] | g.v[1] | g.v[2] | g.v[3] | g.v[4] | g.v[5] | g.v[6] | g.v[7] | g.v[8]) == 0);
+  // g == 0 now and f == +-1 (f == r, d == 0 for x == 0): sign(f) * d == R^2 / y (mod r) with |d| < 22 r.
+  // t = 32 r + sign(f) * d (the negation is a two's complement over the limbs: ~d + 1), then reduce.
+  Fr t;
+  {
+    const bool neg = (int32_t)f.v[NL - 1] < 0;
+    u32 c = neg ? 1u : 0u;
+#pragma unroll
+    for (int i = 0; i < NL - 1; i++) {
+      const u32 w = (neg ? (~d.v[i] & MASK29) : d.v[i]) + R32[i] + c;
+      t.v[i] = w & MASK29; c = w >> 29;
+    }
+    t.v[NL - 1] = (u32)((int32_t)(neg ? ~d.v[NL - 1] : d.v[NL - 1]) + (int32_t)R32[NL - 1] + (int32_t)c);   // > 0, < 2^28
+  }
+  t = fr_cond_sub_kr(t, R32); t = fr_cond_sub_kr(t, R16); t = fr_cond_sub_kr(t, R8);
+  t = fr_cond_sub_kr(t, R4); t = fr_cond_sub_kr(t, R2c); t = fr_cond_sub_kr(t, R1);
+  return t;
+}
+
 }  // namespace bjj

@@ -32,7 +32,10 @@ static __constant__ Consts c_K = {
 // (log2 G steps each, no barrier), the 64 group products go through LDS to ONE wave
 // whose 64 lanes invert one group product each (binary GCD), and every thread
 // finishes with 1/x = (1/group product) * (product of the lanes before it) * (after it).
+// CORE selects what the one wave runs: INV_GCD = fr_inv (everyone's default, and their machine code), INV_K1 = fr_inv_k1, the
+// shorter division-step core, which K1 (k_fixed.hip) passes through epilogue_run.
 // ---------------------------------------------------------------------------
+enum : int { INV_GCD = 0, INV_K1 = 1 };
 template <int GROUP>
 __device__ __forceinline__ Fr fr_shfl_up(const Fr& f, int d) {
   Fr r;
@@ -47,7 +50,7 @@ __device__ __forceinline__ Fr fr_shfl_down(const Fr& f, int d) {
   for (int i = 0; i < NL; i++) r.v[i] = __shfl_down(f.v[i], d, GROUP);
   return r;
 }
-template <int BLOCK>
+template <int BLOCK, int CORE = INV_GCD>
 __device__ Fr block_invert(const Fr& x, u32* lds /* NL * 64 words */) {
   constexpr int GROUP = BLOCK / 64;
   const int t = threadIdx.x, gl = t & (GROUP - 1), grp = t / GROUP;
@@ -71,7 +74,7 @@ __device__ Fr block_invert(const Fr& x, u32* lds /* NL * 64 words */) {
     Fr tot;
 #pragma unroll
     for (int i = 0; i < NL; i++) tot.v[i] = lds[i * 64 + l];
-    Fr inv = fr_inv(tot);
+    Fr inv = CORE == INV_K1 ? fr_inv_k1(tot) : fr_inv(tot);
 #pragma unroll
     for (int i = 0; i < NL; i++) lds[i * 64 + l] = inv.v[i];
   }
@@ -138,10 +141,10 @@ __device__ __forceinline__ void epilogue_finish(Fr& inv, uint8_t* out_item, uint
   }
 }
 // out: 64 bytes per item (32 with EPI_COMPRESS); xy: where phase 1 stashed X, Y, 64 bytes per item (== out for the affine form)
-template <int BLOCK = BJJ_EPI_BLOCK, unsigned FORM = EPI_AFFINE>
+template <int BLOCK = BJJ_EPI_BLOCK, unsigned FORM = EPI_AFFINE, int CORE = INV_GCD>
 __device__ __forceinline__ void epilogue_run(Fr run, size_t n, size_t tid, size_t nthreads, uint8_t* out, u32* scratch,
                                              u32* lds, uint8_t* xy = nullptr) {
-  Fr inv = fr_mul(block_invert<BLOCK>(run, lds), fr_one_plain());  // out of Montgomery form once per lane
+  Fr inv = fr_mul(block_invert<BLOCK, CORE>(run, lds), fr_one_plain());  // out of Montgomery form once per lane
   if (tid >= n) return;
   size_t cnt = (n - tid + nthreads - 1) / nthreads;
 #pragma unroll 1

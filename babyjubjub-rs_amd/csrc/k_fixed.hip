@@ -13,6 +13,10 @@
 #ifndef BJJ_K1_NBUF
 #define BJJ_K1_NBUF 2
 #endif
+// the inversion core of K1's epilogue (A/B knob; default: the division-step core, fr.hpp: fr_inv_k1)
+#ifndef BJJ_K1_INV_CORE
+#define BJJ_K1_INV_CORE INV_K1
+#endif
 
 // ---------------------------------------------------------------------------
 // init: fixed-base table (layout and recoding: bjj_device.hpp "fixed base").
@@ -69,7 +73,7 @@ __device__ __forceinline__ void mul_fixed_base_body(const u32* __restrict__ tabl
     Ext p = fixed_base_mul(fb, W, nwin, sc, c_K);
     if (valid) epilogue_stash(p, run, ((FORM & EPI_COMPRESS) ? xy : out) + i * 64, scratch + i * 16);
   }
-  epilogue_run<BLOCK, FORM>(run, n, tid, nthreads, out, scratch, lds, xy);
+  epilogue_run<BLOCK, FORM, BJJ_K1_INV_CORE>(run, n, tid, nthreads, out, scratch, lds, xy);
 }
 // Two shapes of the same kernel:
 //  * bjj_k_mul_fixed_base: ONE workgroup of BJJ_K1_BLOCK = 512 lanes per CU (2 waves per SIMD, two staging areas per wave,
@@ -102,7 +106,7 @@ __device__ __forceinline__ void mul_fixed_base_scan_body(const u32* __restrict__
     Ext p = fixed_base_mul(fb, W, nwin, sc, c_K);
     epilogue_stash(p, run, ((FORM & EPI_COMPRESS) ? xy : out) + i * 64, scratch + i * 16);
   }
-  epilogue_run<BJJ_EPI_BLOCK, FORM>(run, n, tid, nthreads, out, scratch, lds, xy);
+  epilogue_run<BJJ_EPI_BLOCK, FORM, BJJ_K1_INV_CORE>(run, n, tid, nthreads, out, scratch, lds, xy);
 }
 __global__ void __launch_bounds__(BJJ_EPI_BLOCK, 1) bjj_k_mul_fixed_base_scan(const u32* __restrict__ table, int W, int nwin,
                                                                         const uint8_t* __restrict__ scalars, size_t n,

@@ -1,0 +1,64 @@
+"""fr_inv_k1 (babyjubjub-rs_amd/csrc/fr.hpp: the division-step inversion of K1's epilogue) on the CPU, built by
+tests/emul/emul_inv_k1.cpp with BJJ_DEBUG_BOUNDS -- the growth bound of (d, e), the exactness of every division by 2^29 and
+g == 0 after the 21 batches are asserted on every call -- against fr_inv_fermat AND fr_inv_gcd, byte for byte after fr_canon,
+and against Python integers.  Inputs are raw representatives below 2r, as K1's epilogue hands them over."""
+import ctypes
+import os
+import subprocess
+
+import pytest
+
+from conftest import ROOT, le32
+
+Q = 21888242871839275222246405745257275088548364400416034343698204186575808495617   # r
+R = 1 << 261
+
+
+@pytest.fixture(scope="module")
+def invlib():
+    d = os.path.join(ROOT, "tests", "emul")
+    so = os.path.join(d, "libbjj_emul_inv_k1.so")
+    srcs = [os.path.join(d, "emul_inv_k1.cpp"), os.path.join(ROOT, "babyjubjub-rs_amd", "csrc", "fr.hpp")]
+    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
+        r = subprocess.run(["g++", "-O2", "-g", "-std=c++17", "-shared", "-fPIC", "-pthread", "-o", so, srcs[0]],
+                           stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        assert r.returncode == 0, r.stdout
+    lib = ctypes.CDLL(so)
+    lib.emul_inv_k1_splitmix.restype = ctypes.c_long
+    lib.emul_inv_k1_splitmix.argtypes = [ctypes.c_ulonglong, ctypes.c_long, ctypes.c_char_p]
+    return lib
+
+
+def _check(lib, xs):
+    out = ctypes.create_string_buffer(32)
+    for x in xs:
+        assert 0 <= x < 2 * Q
+        assert lib.emul_inv_k1_one(le32(x), out) == 1, "the three cores disagree on %#x" % x
+        # X = x R  ->  R / x = R^2 / X; 0 (and r) -> 0
+        want = R * R * pow(x, Q - 2, Q) % Q
+        assert int.from_bytes(out.raw, "little") == want, hex(x)
+
+
+def test_edges(invlib):
+    _check(invlib, [0, 1, 2, Q - 1, Q, Q + 1, 2 * Q - 1, R % Q, R * R % Q])
+
+
+def test_powers_of_two(invlib):
+    _check(invlib, [1 << k for k in range(255)] + [(1 << k) - 1 for k in range(255)])   # 2^254 < 2r < 2^255
+
+
+def test_short_operands(invlib):
+    """top limbs zero: 60, 90 and 120 significant bits"""
+    xs = []
+    for bits in (60, 90, 120):
+        xs += [(1 << bits) - 1, 1 << (bits - 1), (1 << (bits - 1)) + 1,
+               (0x9e3779b97f4a7c15f39cc0605cedc835 * (bits + 1)) % (1 << bits) | (1 << (bits - 1)),
+               (0xc2b2ae3d27d4eb4f165667b19e3779f9 * (bits + 3)) % (1 << bits) | (1 << (bits - 1)) | 1]
+    _check(invlib, xs)
+
+
+def test_splitmix_values(invlib):
+    """10^5 SplitMix64 values below 2r, compared inside the harness (8 streams on 8 threads)"""
+    first_bad = ctypes.create_string_buffer(32)
+    bad = invlib.emul_inv_k1_splitmix(0x6b315f696e76, 100000, first_bad)
+    assert bad == 0, "first disagreement at %#x" % int.from_bytes(first_bad.raw, "little")
