@@ -1,5 +1,7 @@
 // TEST-ONLY kernels (not part of libbjj_hip.so): run the field / curve primitives that SHIP -- the inline-asm column
 // multiplier fr_mul_columns / fr_sqr_columns, the asm dot products with scalar-register matrix operands, fr_inv_gcd,
+// fr_inv_k1 (the division-step inversion of K1's epilogue: the eight limb products of a batch are one asm statement of
+// v_mad_i64_i32 in the device build only, so its directed inputs have to run HERE -- op FZ_INV_K1),
 // ext_madd / ext_dbl / ext_add_pn -- on raw limb vectors chosen by the test, so that the lazy-reduction contract of
 // fr.hpp:14-20 ("limbs < 2^30, values < 13 r") is asserted on the device code itself and not only on the portable form
 // the CPU harness (tests/emul) executes.  Built twice from the product's own headers:
@@ -24,7 +26,7 @@ __device__ __forceinline__ Fr ld(const u32* p) { Fr f; for (int i = 0; i < NL; i
 __device__ __forceinline__ void st(u32* p, const Fr& f) { for (int i = 0; i < NL; i++) p[i] = f.v[i]; }
 
 enum { FZ_MUL = 0, FZ_SQR = 1, FZ_INV = 2, FZ_DOT6 = 3, FZ_DOT15 = 4, FZ_DOT151 = 5, FZ_DOT2ADD = 6, FZ_MADD = 7, FZ_DBL = 8,
-       FZ_ADDPN = 9, FZ_DBL_NOT = 10, FZ_MADD_NOT = 11, FZ_CONSTS = 20 };
+       FZ_ADDPN = 9, FZ_DBL_NOT = 10, FZ_MADD_NOT = 11, FZ_INV_K1 = 12, FZ_CONSTS = 20 };
 
 // a, b, c: per-item records of wa / wb / wc limb-words; out: wo words per item.  `row` selects the wave-uniform
 // constant operands of the dot products (Poseidon matrix rows / sparse-round vectors), as in the kernels that ship.
@@ -37,6 +39,7 @@ __global__ void __launch_bounds__(256) fz_kernel(const u32* __restrict__ a, cons
     if (OP == FZ_MUL) st(out + i * 9, fr_mul(ld(a + i * 9), ld(b + i * 9)));
     if (OP == FZ_SQR) st(out + i * 9, fr_sqr(ld(a + i * 9)));
     if (OP == FZ_INV) st(out + i * 9, fr_inv(ld(a + i * 9)));
+    if (OP == FZ_INV_K1) st(out + i * 9, fr_inv_k1(ld(a + i * 9)));
     if (OP == FZ_DOT6) {
       Fr x[6];
       for (int j = 0; j < 6; j++) x[j] = ld(b + i * 54 + j * 9);
@@ -93,6 +96,7 @@ extern "C" __attribute__((visibility("default"))) int fz_run(int op, const uint3
   switch (op) {
     FZ_CASE(FZ_MUL); FZ_CASE(FZ_SQR); FZ_CASE(FZ_INV); FZ_CASE(FZ_DOT6); FZ_CASE(FZ_DOT15); FZ_CASE(FZ_DOT151);
     FZ_CASE(FZ_DOT2ADD); FZ_CASE(FZ_MADD); FZ_CASE(FZ_DBL); FZ_CASE(FZ_ADDPN); FZ_CASE(FZ_DBL_NOT); FZ_CASE(FZ_MADD_NOT);
+    FZ_CASE(FZ_INV_K1);
     case FZ_CONSTS: hipLaunchKernelGGL(fz_consts, dim3(1), dim3(64), 0, st_, out); break;
     default: return -1;
   }

@@ -2,14 +2,21 @@
 dot products, the binary-GCD inversion and the extended-coordinate formulas, run on the GPU on adversarial raw limb
 vectors -- all-ones 29- and 30-bit limbs, values at 2r / 4r / 13r, the largest top limbs the contract of
 babyjubjub-rs_amd/csrc/fr.hpp:14-20 allows -- and checked (i) against Python integers on samples and (ii) bit for bit
-against the compiler-scheduled portable columns (-DBJJ_NO_ASM_COLUMNS) on 10^7 random pairs."""
+against the compiler-scheduled portable columns (-DBJJ_NO_ASM_COLUMNS) on 10^7 random pairs.
+Also here: fr_inv_k1, the division-step inversion of K1's epilogue, whose v_mad_i64_i32 asm statement exists in the device
+build only -- on the directed set of tests/divstep_ref.py (edges, 2^k, 2^k - 1, [r, 2r) representatives, short operands,
+zero low limbs; both end states f = +1 / f = -1 proven present by the plain-integer model) and on 10^6 random operands,
+asm == portable == binary GCD limb for limb -- and block_invert (csrc/k_common.hpp) with chosen per-lane values in the three
+instances that ship, including a grid of more than 256 workgroups, where the choice of the inverting wave changes."""
 import ctypes
+import functools
 import os
 import subprocess
 
 import numpy as np
 import pytest
 
+import divstep_ref as ds
 from conftest import ROOT
 
 pytestmark = pytest.mark.gpu
@@ -19,7 +26,7 @@ RADIX = 1 << 261
 RINV = pow(RADIX, -1, R_MOD)
 TOP_R = R_MOD >> 232            # 3171406: top limb of r
 A_REF, D_REF = 168700, 168696
-OPS = dict(mul=0, sqr=1, inv=2, dot6=3, dot15=4, dot151=5, dot2add=6, madd=7, dbl=8, addpn=9, dbl_not=10, madd_not=11, consts=20)
+OPS = dict(mul=0, sqr=1, inv=2, dot6=3, dot15=4, dot151=5, dot2add=6, madd=7, dbl=8, addpn=9, dbl_not=10, madd_not=11, inv_k1=12, consts=20)
 
 
 def val(limbs):
@@ -172,6 +179,164 @@ def test_inversion_on_device(fz):
         # Montgomery inverse: x = R^2 / v  (0 -> 0), canonical
         want = 0 if v % R_MOD == 0 else RADIX * RADIX * pow(v, -1, R_MOD) % R_MOD
         assert val(x[i]) == want, hex(v)
+
+
+def below(rows, bound):
+    """per row of N-form limbs (limbs 0..7 < 2^29): value < bound, vectorised"""
+    b = nform(bound)
+    lt, eq = np.zeros(rows.shape[0], bool), np.ones(rows.shape[0], bool)
+    for i in range(8, -1, -1):
+        lt |= eq & (rows[:, i] < b[i])
+        eq &= rows[:, i] == b[i]
+    return lt
+
+
+def vals(rows):
+    """the Python integers of many N-form rows (limbs 0..7 < 2^29) at once: pairs of limbs are joined in numpy first"""
+    x = rows.astype(np.uint64)
+    assert int(x[:, :8].max()) < (1 << 29)
+    c = [(x[:, 2 * j] | (x[:, 2 * j + 1] << np.uint64(29))).tolist() for j in range(4)] + [x[:, 8].tolist()]
+    return [a | (b << 58) | (cc << 116) | (d << 174) | (e << 232) for a, b, cc, d, e in zip(*c)]
+
+
+def test_k1_inversion_core_on_device(fz):
+    """fr_inv_k1 as the device compiles it (asm: the v_mad_i64_i32 statement; portable: the C++ branch under hipcc) on raw
+    operands below 2r.  Directed set (tests/divstep_ref.py): asm == portable == fr_inv limb for limb, every output equals
+    R^2 / v in Python integers, canonical.  The plain-integer model proves the set's coverage from the inputs alone: at least
+    100 operands end with f = -1 (the negation of d) and at least 100 with f = +1.  Largest step at which g reaches 0 over
+    the set: 527 of 609 (printed; informational).  Bulk: 10^6 random operands below 2r, asm == portable == fr_inv, every
+    997th against Python integers."""
+    import torch
+    ops = ds.directed_operands()
+    model = [ds.divsteps(v) for v in ops]
+    ends = {s: sum(1 for m in model if m[0] == s) for s in (1, -1)}
+    assert ends[1] >= 100 and ends[-1] >= 100, ends
+    print("\n[fr_inv_k1] %d directed operands: %d end with f = +1, %d with f = -1; g reaches 0 after at most %d steps"
+          % (len(ops), ends[1], ends[-1], max(m[1] for m in model)))
+    n = len(ops)
+    a = dev(np.array([nform(v) for v in ops], dtype=np.uint64).astype(np.uint32))
+    k_asm, k_port = fz[0].run("inv_k1", a, None, None, n, 9), fz[1].run("inv_k1", a, None, None, n, 9)
+    g_asm, g_port = fz[0].run("inv", a, None, None, n, 9), fz[1].run("inv", a, None, None, n, 9)
+    hk = host(k_asm)
+    for i, v in enumerate(ops):             # Python integers first: a failure names the operand
+        want = 0 if v % R_MOD == 0 else RADIX * RADIX * pow(v, -1, R_MOD) % R_MOD
+        assert val(hk[i]) == want, hex(v)
+        assert model[i][0] * model[i][2] % R_MOD == want
+        check_nform_below(hk[i], R_MOD)
+    for other in (k_port, g_asm, g_port):
+        assert torch.equal(k_asm, other), [hex(ops[i]) for i in torch.nonzero((k_asm != other).any(dim=1))[:10, 0].tolist()]
+    # ---- bulk
+    rng = np.random.default_rng(0x6b31)
+    keep = 1_000_000
+    x = random_limbs(rng, keep + keep // 64, 1, 2 * TOP_R)
+    ok = below(x, 2 * R_MOD)
+    assert 1.0 - ok.mean() < 0.01            # a property of the generator alone
+    x = x[ok][:keep]
+    assert x.shape[0] == keep
+    a = dev(x)
+    k_asm = fz[0].run("inv_k1", a, None, None, keep, 9)
+    assert torch.equal(k_asm, fz[1].run("inv_k1", a, None, None, keep, 9))
+    assert torch.equal(k_asm, fz[0].run("inv", a, None, None, keep, 9))
+    idx = np.arange(0, keep, 997)
+    for v, got in zip(vals(x[idx]), host(k_asm[idx])):
+        assert val(got) == RADIX * RADIX * pow(v, -1, R_MOD) % R_MOD, hex(v)
+        check_nform_below(got, R_MOD)
+
+
+# ---- block_invert (csrc/k_common.hpp) on per-lane values chosen here (tests/devfuzz/blockinv.hip) ------------------------
+BI_VARIANTS = {"512_k1": 0, "256_k1": 1, "512_gcd": 2}
+BI_GRID = 520       # > 256 workgroups: (blockIdx.x + (blockIdx.x >> 8)) % (BLOCK / 64) with a non-zero shift term
+
+
+@functools.lru_cache(maxsize=None)
+def _blockinv_lib():
+    d = os.path.join(ROOT, "tests", "devfuzz")
+    so = os.path.join(d, "libbjj_blockinv_test.so")
+    if not os.path.exists(so) or os.path.getmtime(os.path.join(d, "blockinv.hip")) > os.path.getmtime(so):
+        r = subprocess.run(["make", "-s"], cwd=d, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        assert r.returncode == 0, r.stdout
+    import torch  # noqa: F401
+    lib = ctypes.CDLL(so)
+    vp = ctypes.c_void_p
+    lib.bi_run.argtypes = [ctypes.c_int, vp, vp, ctypes.c_int, vp]
+    return lib
+
+
+def _inverting_wave(block_index, block):
+    return (block_index + (block_index >> 8)) % (block // 64)
+
+
+@functools.lru_cache(maxsize=None)
+def _blockinv_inputs(block):
+    """(names, rows of the one-workgroup cases -- case j is workgroup j --, rows of the 520-workgroup grid): Montgomery-form
+    values, never 0, N-form below 2r.  Built once per workgroup size and shared by the variants; nobody writes to it."""
+    import random
+    rnd = random.Random(0x626c6b + block)
+    r, group, one = R_MOD, block // 64, RADIX % R_MOD
+    some = lambda: rnd.randrange(1, r)  # noqa: E731
+    cases = [("every lane 1*R", [one] * block)]
+    spots = [("lane 0", 0), ("lane GROUP-1", group - 1), ("lane GROUP", group), ("the last lane", block - 1)]
+    for name, lane in spots + [("a lane of the inverting wave", None)]:
+        if lane is None:
+            lane = 64 * _inverting_wave(len(cases), block) + 17
+        v = [one] * block
+        v[lane] = some()
+        cases.append(("one random value in %s, the rest 1*R" % name, v))
+    cases.append(("every lane (r-1)*R: group products are +-1", [(r - 1) * RADIX % r] * block))
+    cases.append(("every lane the same random value", [some()] * block))
+    cases.append(("every lane random, half of them in [r, 2r)", [some() + (r if rnd.random() < 0.5 else 0) for _ in range(block)]))
+    cases.append(("lane k holds 2^k * R", [pow(2, k, r) * RADIX % r for k in range(block)]))
+    rows = np.array([nform(v) for _, lanes in cases for v in lanes], dtype=np.uint64).astype(np.uint32)
+    grid = random_limbs(np.random.default_rng(block), BI_GRID * block, 1, 2 * TOP_R)
+    grid = grid[below(grid, 2 * R_MOD) & grid.any(axis=1)]
+    assert grid.shape[0] >= (BI_GRID * block * 99) // 100      # a property of the generator alone
+    grid = np.concatenate([grid, grid[:BI_GRID * block - grid.shape[0]]])
+    for a in (rows, grid):
+        assert a.any(axis=1).all() and below(a, 2 * R_MOD).all()
+    return [c[0] for c in cases], rows, grid
+
+
+@functools.lru_cache(maxsize=None)
+def _blockinv_outputs(variant):
+    import torch
+    lib, block = _blockinv_lib(), 256 if variant == 1 else 512
+    outs = []
+    for rows in _blockinv_inputs(block)[1:]:
+        assert rows.shape[0] % block == 0 and rows.shape[1] == 9
+        a = dev(rows)
+        out = torch.zeros_like(a)
+        assert lib.bi_block(variant) == block and a.numel() == out.numel() == rows.shape[0] * 9
+        assert lib.bi_run(variant, a.data_ptr(), out.data_ptr(), rows.shape[0] // block, None) == 0
+        torch.cuda.synchronize()
+        outs.append(host(out).reshape(-1, 9))
+    return outs
+
+
+@pytest.mark.parametrize("variant", list(BI_VARIANTS), ids=list(BI_VARIANTS))
+def test_block_invert_directed_lanes(variant):
+    """block_invert<BLOCK, CORE> for (512, fr_inv_k1), (256, fr_inv_k1), (512, fr_inv) with the values of every lane chosen
+    here: all ones (idle lanes of a short batch), one value among ones at the edges of a group, of the workgroup and inside the
+    inverting wave, (r-1)*R everywhere, one value everywhere, [r, 2r) representatives, 2^k*R, and 520 workgroups of random
+    values (every wave of the workgroup inverts, block indices >= 256 included).  Every lane in Python integers:
+    out * x == R^2 (mod r), out is N-form below 2r (what epilogue_run's next fr_mul requires); the two cores agree modulo r."""
+    v = BI_VARIANTS[variant]
+    block = 256 if v == 1 else 512
+    names, small, grid = _blockinv_inputs(block)
+    picks = {(_inverting_wave(b, block), b >= 256) for b in range(BI_GRID)}      # what the grid is for: every wave inverts,
+    assert picks == {(w, hi) for w in range(block // 64) for hi in (False, True)}    # with and without the shift term
+    k2 = RADIX * RADIX % R_MOD
+    for rows, out in zip((small, grid), _blockinv_outputs(v)):
+        assert out.shape == rows.shape
+        assert int(out[:, :8].max()) < (1 << 29)
+        bad = np.nonzero(~below(out, 2 * R_MOD))[0]
+        assert bad.size == 0, (variant, "not below 2r", bad[:10] // block, bad[:10] % block)
+        for i, (x, y) in enumerate(zip(vals(rows), vals(out))):
+            assert x * y % R_MOD == k2, (variant, names[i // block] if rows is small else "grid, workgroup %d" % (i // block),
+                                         "lane %d" % (i % block), hex(x))
+    if v == 2:
+        for a, b in zip(_blockinv_outputs(0), _blockinv_outputs(2)):
+            bad = [i for i, (x, y) in enumerate(zip(vals(a), vals(b))) if (x - y) % R_MOD]
+            assert not bad, ("fr_inv_k1 and fr_inv disagree modulo r", [(i // block, i % block) for i in bad[:10]])
 
 
 def test_asm_dot_products(fz):
