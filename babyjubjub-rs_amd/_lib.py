@@ -48,6 +48,9 @@ EXPORTED_SYMBOLS = (
 )
 # every symbol the extension headers declare (include/bjj_hip_msm_batch.h); EXPORTED_SYMBOLS stays the mirror of bjj_hip.h
 EXT_SYMBOLS = ("bjj_msm_batch", "bjj_msm_batch_dev")
+# ... and include/bjj_hip_bases.h
+BASES_SYMBOLS = ("bjj_base_create", "bjj_base_free", "bjj_base_info", "bjj_base_check", "bjj_mul_bases", "bjj_mul_bases_dev")
+BJJ_MAX_BASES = 8
 
 
 class BjjInfo(ctypes.Structure):
@@ -182,6 +185,12 @@ def load():
     lib.bjj_msm_dev.argtypes = [vp, vp, vp, sz, ci, vp, vp, vp]
     lib.bjj_msm_batch.argtypes = [vp, vp, vp, sz, vp, sz, ci, vp, vp]
     lib.bjj_msm_batch_dev.argtypes = [vp, vp, vp, sz, vp, sz, ci, vp, vp, vp]
+    lib.bjj_base_create.argtypes = [vp, vp, ci, ctypes.POINTER(vp)]
+    lib.bjj_base_free.argtypes = [vp, vp]
+    lib.bjj_base_info.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_uint64)]
+    lib.bjj_base_check.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_uint64)]
+    lib.bjj_mul_bases.argtypes = [vp, ctypes.POINTER(vp), ci, ctypes.POINTER(vp), sz, vp]
+    lib.bjj_mul_bases_dev.argtypes = [vp, ctypes.POINTER(vp), ci, ctypes.POINTER(vp), sz, vp, vp]
     # multi-GPU
     pd = ctypes.POINTER(ctypes.c_double)
     lib.bjj_multi_init.argtypes = [ctypes.POINTER(ci), ci, ci, ctypes.POINTER(vp)]

@@ -90,6 +90,8 @@ class Context:
 
     def close(self):
         if getattr(self, "handle", None):
+            for b in list(getattr(self, "_bases", [])):               # FixedBase objects that were never closed
+                b.close()
             for ptr in list(getattr(self, "_pinned", {}).values()):   # arrays from host_empty that were never released
                 self.lib.bjj_host_free(self.handle, ptr)
             self._pinned = {}
@@ -302,6 +304,51 @@ class Context:
                  "bjj_msm_batch")
         return out.reshape(m, 64), status
 
+    # ---- fixed-base tables for caller-chosen points (include/bjj_hip_bases.h) ----
+    def base(self, point, window_bits=0):
+        """a reusable fixed-base table for `point` ((x, y) ints, a Point, or a 64-byte record) -> FixedBase (bjj_base_create).
+        window_bits: 0 = 16, or 4..28.  BjjError for a point that is not on the curve.  Freed with close() or with the context."""
+        if isinstance(point, Point):
+            point = (point.x, point.y)
+        rec = _as_u8([tuple(point)] if isinstance(point, (tuple, list)) else point, 64, "point")
+        if rec.size != 64:
+            raise BjjError("base: exactly one point")
+        h = ctypes.c_void_p()
+        self._ck(self.lib.bjj_base_create(self.handle, rec.ctypes.data, int(window_bits), ctypes.byref(h)), "bjj_base_create")
+        b = FixedBase(self, h)
+        self._bases = getattr(self, "_bases", [])
+        self._bases.append(b)
+        return b
+
+    def _base_args(self, bases, arrays, what):
+        t = len(bases)
+        if len(arrays) != t:
+            raise BjjError("%s: %d bases but %d scalar arrays" % (what, t, len(arrays)))
+        handles = []
+        for b in bases:
+            if b is not None and (not isinstance(b, FixedBase) or b.ctx is not self or not b.handle):
+                raise BjjError("%s: a base is a live FixedBase of this context, or None for B8" % what)
+            handles.append(b.handle.value if b is not None else None)
+        return (ctypes.c_void_p * max(t, 1))(*handles), (ctypes.c_void_p * max(t, 1))(*arrays)
+
+    def mul_bases(self, bases, scalars):
+        """out[i] = sum_j scalars[j][i] * P_j in one launch (bjj_mul_bases): bases = FixedBase objects, None = B8; scalars = one
+        array of n 32-byte records (or n ints) per base.  Byte for byte the fold of mul_scalar with PointProjective::add, then
+        affine() (lib.rs:149-164, 88-131, 70-85).  -> (n, 64)"""
+        arrs = [_as_u8(s, 32, "scalars") for s in scalars]
+        n = arrs[0].size // 32 if arrs else 0
+        if any(a.size != n * 32 for a in arrs):
+            raise BjjError("mul_bases: the scalar arrays differ in length")
+        hb, hs = self._base_args(list(bases), [a.ctypes.data for a in arrs], "mul_bases")
+        out = np.empty(n * 64, dtype=np.uint8)
+        self._ck(self.lib.bjj_mul_bases(self.handle, hb, len(arrs), hs, n, out.ctypes.data), "bjj_mul_bases")
+        return out.reshape(n, 64)
+
+    def mul_bases_dev(self, bases, d_scalars, n, d_out, stream=0):
+        """bjj_mul_bases_dev: d_scalars = one device address per base (n 32-byte records each), d_out = n 64-byte records"""
+        hb, hs = self._base_args(list(bases), [int(p) for p in d_scalars], "mul_bases_dev")
+        self._ck(self.lib.bjj_mul_bases_dev(self.handle, hb, len(d_scalars), hs, n, d_out, stream), "bjj_mul_bases_dev")
+
     def set_signer_constant_time(self, on=True):
         """signer hardening: public_keys / sign / sign_schnorr scan a small 4-bit table instead of indexing the big one
         with secret digits -- no secret-dependent address or branch; bit-identical results, ~2x slower sign"""
@@ -475,6 +522,36 @@ class Context:
     def schnorr_verify_dev(self, d_pk, d_r, d_s, d_msg, n, d_ok, stream=0):
         self._ck(self.lib.bjj_schnorr_verify_dev(self.handle, d_pk, d_r, d_s, d_msg, n, d_ok, stream),
                  "bjj_schnorr_verify_dev")
+
+
+class FixedBase:
+    """A fixed-base table for one curve point (bjj_base, include/bjj_hip_bases.h); made by Context.base()."""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self.handle = ctx, handle
+
+    def close(self):
+        """bjj_base_free: waits for the context's enqueued work, then releases the table"""
+        if getattr(self, "handle", None) and getattr(self.ctx, "handle", None):
+            self.ctx._ck(self.ctx.lib.bjj_base_free(self.ctx.handle, self.handle), "bjj_base_free")
+            self.ctx._bases.remove(self)
+        self.handle = None
+
+    def info(self):
+        """-> (window_bits, n_windows, table_bytes)"""
+        w, nw, tb = ctypes.c_int(), ctypes.c_int(), ctypes.c_uint64()
+        self.ctx._ck(self.ctx.lib.bjj_base_info(self.handle, ctypes.byref(w), ctypes.byref(nw), ctypes.byref(tb)), "bjj_base_info")
+        return w.value, nw.value, tb.value
+
+    def check(self):
+        """number of violated link conditions of the table (0 = sound), checked on the device"""
+        bad = ctypes.c_uint64(0)
+        self.ctx._ck(self.ctx.lib.bjj_base_check(self.ctx.handle, self.handle, ctypes.byref(bad)), "bjj_base_check")
+        return bad.value
+
+    def mul(self, scalars):
+        """scalars[i] * P for every i -> (n, 64): Context.mul_bases with this one base"""
+        return self.ctx.mul_bases([self], [scalars])
 
 
 class MultiContext:

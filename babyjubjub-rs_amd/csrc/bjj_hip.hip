@@ -37,7 +37,9 @@
 
 #include "../../include/bjj_hip.h"
 #include "../../include/bjj_hip_msm_batch.h"
+#include "../../include/bjj_hip_bases.h"
 #include "bjj_device.hpp"
+#include "bases.hpp"
 #include "bjj_launch.hpp"
 #include "msm.hpp"
 #include "copy_pool.hpp"
@@ -152,6 +154,7 @@ struct ScratchSet {
   DevBlock<uint8_t> codec;     // verify_compressed: n * (64 pk + 64 R + 32 s + 2 flags) bytes; public_keys: the scalar keys (wiped)
   DevBlock<uint8_t> xy;        // K1 with compressed output: n * 64 B, the phase-1 stash of X, Y (the 32-byte output slot cannot hold it)
   DevBlock<uint8_t> msm;       // bjj_msm: one block per call laid out by bjjk::msm_layout (+ the host form's copies of the inputs)
+  DevBlock<uint8_t> bases_io;  // bjj_mul_bases, host form: the t scalar arrays and the results of one call (wiped: ElGamal's r passes through)
   // Ordering of the set: every call that uses it records `ev_last` on its stream after enqueueing, and a call on a
   // DIFFERENT stream first makes its stream wait for it.  Calls return before the work runs, so "serialised by the
   // caller" alone would not order execution.
@@ -167,6 +170,15 @@ struct StreamMark {
   bool used = false;
   uint64_t last_use = 0;
 };
+// A fixed-base table for a caller-chosen curve point (include/bjj_hip_bases.h): the layout of the context's B8 table with
+// base_nwin(W) windows (bases.hpp).  Owned by its context (bjj_ctx::user_bases); a handle that exists is a table that passed its check.
+struct bjj_base {
+  bjj_ctx* ctx = nullptr;
+  int W = 0, nwin = 0;
+  u32 xy[16] = {0};          // the point as given (the kernels reduce the coordinates mod r)
+  DevBlock<u32> table;       // [window][digit 0 .. 2^(W-1)] x 128 B
+  DevBlock<u32> bases;       // P_j = 2^(W j) * P, one Niels entry per window
+};
 struct bjj_ctx {
   int device = 0;
   int cus = 0;
@@ -177,6 +189,8 @@ struct bjj_ctx {
   // business); the others: resident 256-lane workgroups per CU
   int lanes_fixed = 512, lanes_var = 512;
   int lanes_fixed_2x256 = 512;   // resident lanes per CU of K1's two-workgroup shape
+  int lanes_bases = 512;         // resident lanes per CU of bjj_k_mul_bases
+  std::vector<bjj_base*> user_bases;   // the tables bjj_base_create made and bjj_base_free has not released yet
   int verify_mode = -1;          // -1 = per call (persistent waves for one launch > 2^21 items that runs alone, groups otherwise), 0 / 1 = forced (BJJ_VERIFY_DISPATCH)
   int k2_variant = -1;           // -1 = per call (tiles for a launch that runs alone, grid-strided while another is in flight), 0 / 1 = forced (BJJ_K2_VARIANT)
   int k1_variant = -1;           // -1 = per call (two-workgroup shape while another launch of the context is in flight), 0 / 1 = forced (BJJ_K1_VARIANT)
@@ -1035,6 +1049,8 @@ static void ctx_destroy(bjj_ctx* c) {
     if (S.ev_last) hipEventDestroy(S.ev_last);
   }
   for (StreamMark& k : c->marks) if (k.ev) hipEventDestroy(k.ev);
+  for (bjj_base* b : c->user_bases) delete b;   // tables the caller never freed
+  c->user_bases.clear();
   delete c->pool;   // joins the copy workers
   c->pool = nullptr;
   for (hipEvent_t e : c->ev_in) hipEventDestroy(e);
@@ -1075,7 +1091,7 @@ int bjj_init(int device, int window_bits, bjj_ctx** out_ctx) {
   c->cus = prop.multiProcessorCount;
   // key-derived material passes through these blocks (scalar keys in the codec records, keys in the staging levels): zeroed before they are freed
   c->dstage.wipe = true;
-  for (ScratchSet& S : c->set) S.codec.wipe = true;
+  for (ScratchSet& S : c->set) S.codec.wipe = S.bases_io.wipe = true;
   for (int b = 0; b < BJJ_PIPE_BUFS; b++) c->pin_in[b].wipe = c->pin_out[b].wipe = true;
   const bool autow = window_bits == BJJ_WINDOW_AUTO;
   int W = window_bits == 0 ? BJJ_DEFAULT_WINDOW_BITS : window_bits;
@@ -1092,6 +1108,7 @@ int bjj_init(int device, int window_bits, bjj_ctx** out_ctx) {
   c->nwin = fixed_nwin(W);
   c->lanes_fixed = bjjk::fixed_base_lanes_per_cu(0);
   c->lanes_fixed_2x256 = bjjk::fixed_base_lanes_per_cu(1);
+  c->lanes_bases = bjjk::bases_lanes_per_cu();
   if (const char* e = getenv("BJJ_VERIFY_DISPATCH")) {
     if (e[0] == '0' || e[0] == '1') c->verify_mode = e[0] - '0';
   }
@@ -1189,14 +1206,19 @@ void bjj_free(bjj_ctx* c) {
   ctx_destroy(c);
 }
 
-int bjj_sync(bjj_ctx* c) {
-  if (!c) return set_err(BJJ_E_INVALID, "bjj_sync: ctx is NULL");
-  ENTER_DEVICE(c->device);
+// waits for everything the context has enqueued, on its own stream and on the callers' (the context's device is current)
+static int ctx_wait_enqueued(bjj_ctx* c) {
   for (ScratchSet& S : c->set)      // work enqueued on a caller's stream
     if (S.have_last && S.last_stream != c->stream) HIPCK(hipEventSynchronize(S.ev_last));
   for (StreamMark& k : c->marks)
     if (k.used) HIPCK(hipEventSynchronize(k.ev));
   HIPCK(hipStreamSynchronize(c->stream));
+  return BJJ_OK;
+}
+int bjj_sync(bjj_ctx* c) {
+  if (!c) return set_err(BJJ_E_INVALID, "bjj_sync: ctx is NULL");
+  ENTER_DEVICE(c->device);
+  { int rc = ctx_wait_enqueued(c); if (rc) return rc; }
   // everything the context enqueued has run: a slot-queue pop that gave up waiting (slot_queue.hpp) is an ERROR of the launches
   // just completed -- reported here instead of a hung GPU; the rings are rebuilt so that the context stays usable
   return ctx_check_slot_queues(c, "bjj_sync");
@@ -2242,6 +2264,150 @@ int bjj_msm_batch(bjj_ctx* c, const uint8_t* pts, const uint8_t* scalars, size_t
              "bjj_msm_batch");
     return BJJ_OK;
   });
+}
+
+// ---- fixed-base tables for caller-chosen points (k_bases.hip, bases.hpp, include/bjj_hip_bases.h) --------------------------------
+#define BJJ_BASE_DEFAULT_WINDOW_BITS 16
+// A x^2 + y^2 == 1 + D x^2 y^2 for the 2 x 8 words of a point record, on the host: a handle is refused before anything is allocated
+static bool point_words_on_curve(const u32 xy[16]) {
+  const u32 a[8] = {168700u, 0, 0, 0, 0, 0, 0, 0}, d[8] = {168696u, 0, 0, 0, 0, 0, 0, 0};
+  const Fr x = fr_to_mont_words(xy), y = fr_to_mont_words(xy + 8);
+  const Fr x2 = fr_sqr(x), y2 = fr_sqr(y);
+  const Fr lhs = fr_add(fr_mul(fr_to_mont_words(a), x2), y2);
+  const Fr rhs = fr_add(fr_one(), fr_mul(fr_to_mont_words(d), fr_mul(x2, y2)));
+  return fr_eq(lhs, rhs);
+}
+static bool base_of_ctx(const bjj_ctx* c, const bjj_base* b) {
+  for (const bjj_base* k : c->user_bases) if (k == b) return true;
+  return false;
+}
+static int base_run_check(bjj_ctx* c, const bjj_base* b, unsigned long long* bad, const char* who) {
+  DevBlock<unsigned long long> d_bad;
+  hipError_t e = d_bad.grow(sizeof(unsigned long long), NO_WAIT);
+  if (e == hipSuccess) e = hipMemsetAsync(d_bad, 0, sizeof(unsigned long long), c->stream);
+  if (e == hipSuccess) e = bjjk::check_base_table(c->stream, c->cus * 8, b->table, b->bases, b->W, b->nwin, b->xy, d_bad);
+  if (e == hipSuccess) e = hipMemcpyAsync(bad, d_bad, sizeof(*bad), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) return set_err(BJJ_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
+  return BJJ_OK;
+}
+int bjj_base_create(bjj_ctx* c, const uint8_t* point_xy, int window_bits, bjj_base** out) {
+  CHECK_CTX(c, "bjj_base_create");
+  if (!point_xy || !out) return set_err(BJJ_E_INVALID, "bjj_base_create: NULL argument");
+  if (window_bits != 0 && (window_bits < 4 || window_bits > BJJ_MAX_WINDOW_BITS))
+    return set_err(BJJ_E_INVALID, "bjj_base_create: window_bits must be 0 (default, 16) or 4..28");
+  u32 xy[16];
+  memcpy(xy, point_xy, 64);
+  if (!point_words_on_curve(xy)) return set_err(BJJ_E_INVALID, "bjj_base_create: the point is not on the curve");
+  ENTER_DEVICE(c->device);
+  bjj_base* b = new (std::nothrow) bjj_base();
+  if (!b) return set_err(BJJ_E_NOMEM, "bjj_base_create: out of host memory");
+  b->ctx = c;
+  b->W = window_bits ? window_bits : BJJ_BASE_DEFAULT_WINDOW_BITS;
+  b->nwin = base_nwin(b->W);
+  memcpy(b->xy, xy, 64);
+  const size_t bytes = fixed_stride(b->W) * (size_t)b->nwin * NIELS_WORDS * sizeof(u32);
+  hipError_t e = b->table.grow(bytes, NO_WAIT);
+  if (e == hipSuccess) e = b->bases.grow((size_t)b->nwin * NIELS_WORDS * sizeof(u32), NO_WAIT);
+  if (e != hipSuccess) {
+    (void)hipGetLastError(); delete b;
+    return set_err(BJJ_E_NOMEM, "bjj_base_create: cannot allocate the table (" + std::to_string(bytes >> 20) + " MB)");
+  }
+  e = bjjk::base_window_bases(c->stream, b->bases, b->W, b->nwin, b->xy);
+  if (e == hipSuccess) e = bjjk::fill_fixed_table(c->stream, b->table, b->bases, b->W, b->nwin);
+  if (e != hipSuccess) { delete b; return set_err(BJJ_E_HIP, std::string("bjj_base_create: table build failed: ") + hipGetErrorString(e)); }
+  unsigned long long bad = 1;   // a handle that exists is a table that passed (the rule of ensure_ct_table)
+  { int rc = base_run_check(c, b, &bad, "bjj_base_create"); if (rc) { delete b; return rc; } }
+  if (bad != 0) { delete b; return set_err(BJJ_E_HIP, "bjj_base_create: the table failed its self-check (" + std::to_string(bad) + " conditions)"); }
+  try { c->user_bases.push_back(b); } catch (...) { delete b; return set_err(BJJ_E_NOMEM, "bjj_base_create: out of host memory"); }
+  *out = b;
+  return BJJ_OK;
+}
+int bjj_base_free(bjj_ctx* c, bjj_base* b) {
+  CHECK_CTX(c, "bjj_base_free");
+  if (!b) return BJJ_OK;
+  if (!base_of_ctx(c, b)) return set_err(BJJ_E_INVALID, "bjj_base_free: not a base of this context");
+  ENTER_DEVICE(c->device);
+  { int rc = ctx_wait_enqueued(c); if (rc) return rc; }   // launches that gather from the table
+  for (size_t i = 0; i < c->user_bases.size(); i++)
+    if (c->user_bases[i] == b) { c->user_bases.erase(c->user_bases.begin() + (long)i); break; }
+  delete b;
+  return BJJ_OK;
+}
+int bjj_base_info(const bjj_base* b, int* window_bits, int* n_windows, uint64_t* table_bytes) {
+  if (!b) return set_err(BJJ_E_INVALID, "bjj_base_info: base is NULL");
+  if (window_bits) *window_bits = b->W;
+  if (n_windows) *n_windows = b->nwin;
+  if (table_bytes) *table_bytes = (uint64_t)b->table.bytes;
+  return BJJ_OK;
+}
+int bjj_base_check(bjj_ctx* c, const bjj_base* b, uint64_t* n_bad) {
+  CHECK_CTX(c, "bjj_base_check");
+  if (!b || !n_bad) return set_err(BJJ_E_INVALID, "bjj_base_check: NULL argument");
+  if (!base_of_ctx(c, b)) return set_err(BJJ_E_INVALID, "bjj_base_check: not a base of this context");
+  ENTER_DEVICE(c->device);
+  unsigned long long bad = 0;
+  { int rc = base_run_check(c, b, &bad, "bjj_base_check"); if (rc) return rc; }
+  *n_bad = (uint64_t)bad;
+  return BJJ_OK;
+}
+// argument checks of both forms; fills the descriptors but for the scalar pointers
+static int mul_bases_check(bjj_ctx* c, const bjj_base* const* bases, int t, const void* const* scalars, size_t n, const char* who,
+                           BasesArgs* A) {
+  if (!c) return set_err(BJJ_E_INVALID, std::string(who) + ": ctx is NULL");
+  if (t < 1 || t > BJJ_MAX_BASES) return set_err(BJJ_E_INVALID, std::string(who) + ": t must be 1..BJJ_MAX_BASES (8)");
+  if (!bases || !scalars) return set_err(BJJ_E_INVALID, std::string(who) + ": NULL array of bases or of scalar arrays");
+  CHECK_N(n);
+  memset(A, 0, sizeof(*A));
+  A->t = t;
+  for (int j = 0; j < t; j++) {
+    const bjj_base* b = bases[j];
+    if (b && !base_of_ctx(c, b)) return set_err(BJJ_E_INVALID, std::string(who) + ": bases[" + std::to_string(j) + "] is not a base of this context");
+    if (n && !scalars[j]) return set_err(BJJ_E_INVALID, std::string(who) + ": scalars[" + std::to_string(j) + "] is NULL");
+    A->b[j].table = b ? b->table.p : c->table.p;
+    A->b[j].W = b ? b->W : c->W;
+    A->b[j].nwin = b ? b->nwin : c->nwin;
+    A->b[j].mod_l = b ? 0 : 1;
+  }
+  return BJJ_OK;
+}
+static_assert(BJJ_MAX_BASES == BJJ_BASES_MAX, "include/bjj_hip_bases.h and bases.hpp disagree");
+int bjj_mul_bases_dev(bjj_ctx* c, const bjj_base* const* bases, int t, const void* const* d_scalars, size_t n, void* d_out, void* stream) {
+  BasesArgs A;
+  { int rc = mul_bases_check(c, bases, t, d_scalars, n, "bjj_mul_bases_dev", &A); if (rc) return rc; }
+  if (n == 0) return BJJ_OK;
+  CHECK_PTR(d_out, "bjj_mul_bases_dev");
+  for (int j = 0; j < t; j++) { CHECK_PTR(d_scalars[j], "bjj_mul_bases_dev"); A.b[j].scalars = (const uint8_t*)d_scalars[j]; }
+  SET_ENTER(c, stream, n, false);
+  LAUNCHCK(bjjk::mul_bases(st, c->cus, c->lanes_bases, A, n, (uint8_t*)d_out, S->scratch), "bjj_mul_bases_dev");
+  SET_LEAVE(c);
+}
+// Synchronous: the t scalar arrays go to the set's block with one copy each (pinned or pageable), one launch, one copy out.
+int bjj_mul_bases(bjj_ctx* c, const bjj_base* const* bases, int t, const uint8_t* const* scalars, size_t n, uint8_t* out_xy) {
+  BasesArgs A;
+  { int rc = mul_bases_check(c, bases, t, (const void* const*)scalars, n, "bjj_mul_bases", &A); if (rc) return rc; }
+  if (n == 0) return BJJ_OK;
+  if (!out_xy) return set_err(BJJ_E_INVALID, "bjj_mul_bases: out_xy is NULL");
+  hipStream_t st = c->stream;
+  ENTER_DEVICE(c->device);
+  ScratchSet* S = pick_set(c, st);
+  { int rc = ensure_scratch(c, S, n); if (rc) return rc; }
+  const size_t sc_bytes = up256(n * 32), o_out = (size_t)t * sc_bytes;
+  if (S->bases_io.grow(o_out + n * 64) != hipSuccess) {
+    (void)hipGetLastError();
+    return set_err(BJJ_E_NOMEM, "bjj_mul_bases: cannot allocate " + std::to_string((o_out + n * 64) >> 20) + " MB of device staging");
+  }
+  { int rc = set_enter(c, S, st); if (rc) return rc; }
+  uint8_t* blk = S->bases_io;
+  for (int j = 0; j < t; j++) {
+    HIPCK(hipMemcpyAsync(blk + (size_t)j * sc_bytes, scalars[j], n * 32, hipMemcpyHostToDevice, st));
+    A.b[j].scalars = blk + (size_t)j * sc_bytes;
+  }
+  LAUNCHCK(bjjk::mul_bases(st, c->cus, c->lanes_bases, A, n, blk + o_out, S->scratch), "bjj_mul_bases");
+  HIPCK(hipMemcpyAsync(out_xy, blk + o_out, n * 64, hipMemcpyDeviceToHost, st));
+  { int rc = set_leave(c, S, st); if (rc) return rc; }
+  HIPCK(hipStreamSynchronize(st));
+  return BJJ_OK;
 }
 
 #pragma GCC visibility pop

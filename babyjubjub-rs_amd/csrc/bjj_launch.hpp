@@ -17,6 +17,8 @@
 #define BJJ_VERIFY_BLOCK 64
 #endif
 
+namespace bjj { struct BasesArgs; }   // bases.hpp: the per-base descriptors of bjj_k_mul_bases
+
 namespace bjjk {
 
 template <typename K>
@@ -44,6 +46,8 @@ int occ_sign_schnorr();
 hipError_t build_fixed_table(hipStream_t st, uint32_t* table, uint32_t* bases, int W, int nwin);
 hipError_t check_fixed_table(hipStream_t st, int grid, const uint32_t* table, const uint32_t* bases, int W, int nwin,
                              unsigned long long* d_bad);
+// the second half of build_fixed_table alone: every entry from the window bases P_j already in `bases` (any base point)
+hipError_t fill_fixed_table(hipStream_t st, uint32_t* table, const uint32_t* bases, int W, int nwin);
 // xy == nullptr: out = 64-byte affine points; xy != nullptr: out = 32-byte Point::compress records, xy = 64 B / item of stash
 hipError_t mul_fixed_base(hipStream_t st, int cus, int lanes_per_cu, int variant, const uint32_t* table, int W, int nwin,
                           const uint8_t* scalars, size_t n, uint8_t* out, uint32_t* scratch, uint8_t* xy = nullptr);
@@ -123,5 +127,13 @@ hipError_t msm_reduce(hipStream_t st, const MsmLayout& L, uint8_t* scratch, cons
 MsmLayout msm_batch_layout(size_t n, size_t m, int c);
 hipError_t msm_batch(hipStream_t st, const MsmLayout& L, const uint8_t* pts, const uint8_t* scalars, size_t n, const uint64_t* offsets,
                      size_t m, uint8_t* scratch, uint8_t* out, unsigned long long* status);
+
+// k_bases.hip: tables for caller-chosen points (xy: the point's 2 x 8 words, any curve point) and bjj_mul_bases,
+// out[i] = sum_j scalars[j][i] * P_j over the A.t tables of A (one item per lane, one 512-lane workgroup per CU)
+int bases_lanes_per_cu();
+hipError_t base_window_bases(hipStream_t st, uint32_t* bases, int W, int nwin, const uint32_t xy[16]);
+hipError_t check_base_table(hipStream_t st, int grid, const uint32_t* table, const uint32_t* bases, int W, int nwin, const uint32_t xy[16],
+                            unsigned long long* d_bad);
+hipError_t mul_bases(hipStream_t st, int cus, int lanes_per_cu, const bjj::BasesArgs& A, size_t n, uint8_t* out, uint32_t* scratch);
 
 }  // namespace bjjk

@@ -147,16 +147,19 @@ int fixed_base_lanes_per_cu(int variant) {   // one grid size serves the affine 
   const int b = variant ? occupancy_of(bjj_k_mul_fixed_base_2x256_c32, 256) * 256 : occupancy_of(bjj_k_mul_fixed_base_c32, BJJ_K1_BLOCK) * BJJ_K1_BLOCK;
   return a < b ? a : b;
 }
-hipError_t build_fixed_table(hipStream_t st, u32* table, u32* bases, int W, int nwin) {
+hipError_t fill_fixed_table(hipStream_t st, u32* table, const u32* bases, int W, int nwin) {
   const size_t entries = fixed_stride(W) * (size_t)nwin;
   // chain length: long enough to amortise the start ladder and the inversion, short enough to fill the GPU
   size_t chain = entries >> 18;
   chain = chain < 4 ? 4 : (chain > 256 ? 256 : chain);
   const size_t chains = ((fixed_stride(W) + chain - 1) / chain) * (size_t)nwin;
-  BJJ_LAUNCH(bjj_k_fixed_window_bases, dim3((nwin + 63) / 64), dim3(64), 0, st, bases, W, nwin);
   BJJ_LAUNCH(bjj_k_build_fixed_table, dim3((unsigned)((chains + BJJ_BLOCK - 1) / BJJ_BLOCK)), dim3(BJJ_BLOCK), 0, st,
                      table, bases, W, nwin, (u32)chain);
   return hipGetLastError();
+}
+hipError_t build_fixed_table(hipStream_t st, u32* table, u32* bases, int W, int nwin) {
+  BJJ_LAUNCH(bjj_k_fixed_window_bases, dim3((nwin + 63) / 64), dim3(64), 0, st, bases, W, nwin);
+  return fill_fixed_table(st, table, bases, W, nwin);
 }
 hipError_t check_fixed_table(hipStream_t st, int grid, const u32* table, const u32* bases, int W, int nwin,
                              unsigned long long* d_bad) {

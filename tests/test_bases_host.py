@@ -1,0 +1,114 @@
+"""bjj_mul_bases without a GPU: the table code and the per-item body of csrc/bases.hpp -- what k_bases.hip launches -- run on the
+CPU by the stand-alone program tests/bases_emul (bound assertions on).  Tables for B8 + T8, a generator of the whole group of
+order 8l, at W = 4, 5 and 12, for the order-2 point (0, -1) at W = 4 and for B8 as a context's own table; every one passes the
+generalised induction check, and every result for t = 1, 2, 3 bases is the oracle's: mul_var_base per term, folded with point_add.
+The same program runs once more built with -fsanitize=address,undefined, directly (no preload)."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from bases_cases import directed, random_scalars
+from conftest import ROOT, ints, pack, unpack
+
+Q = 21888242871839275222246405745257275088548364400416034343698204186575808495617
+B8 = (5299619240641551281634865583518297030282874472190772894086521144482721001553,
+      16950150798460657717958625567821834550301663161624707787222815936182638968203)
+SRC = os.path.join(ROOT, "tests", "bases_emul", "bases_emul.cpp")
+DEPS = [SRC] + [os.path.join(ROOT, "babyjubjub-rs_amd", "csrc", f)
+                for f in ("fr.hpp", "fr_mul_columns.inc", "curve.hpp", "poseidon.hpp", "bjj_device.hpp", "bases.hpp", "bjj_constants.inc")]
+# the cases bases_emul.cpp runs: name -> its tables; the scalar of base j for item i is S[(i + 7 j) % count]
+CASES = {"p4": "P", "p5": "P", "p12": "P", "two4": "2", "b8": "B", "p4+p12": "PP", "b8+p5": "BP", "two4+p4": "2P", "p12+b8": "PB",
+         "p12+b8+two4": "PB2", "p4+p4+p5": "PPP"}
+
+
+def _build(exe, san):
+    if os.path.exists(exe) and all(os.path.getmtime(exe) >= os.path.getmtime(d) for d in DEPS):
+        return None
+    extra = ["-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"] if san else ["-O2"]
+    return subprocess.run(["g++", "-g", "-std=c++17"] + extra + ["-o", exe, SRC], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+
+
+@pytest.fixture(scope="module")
+def inputs(oracle, golden):
+    tors = [ints(t) for t in golden["gpu_expected"]["torsion_points"]]
+    gen = unpack(oracle.point_add(pack([B8]), pack([tors[1]])), 2)[0]          # B8 + T8: order 8l
+    sc = directed((4, 5, 12)) + unpack(random_scalars(200, 0xBA5E5))
+    text = "P %x %x\nS %d\n%s\n" % (gen[0], gen[1], len(sc), "\n".join("%x" % k for k in sc))
+    return {"P": gen, "2": tors[4], "B": B8}, sc, text
+
+
+@pytest.fixture(scope="module")
+def expected(oracle, inputs):
+    """per case the oracle's results, computed once: one mul_var_base per distinct point over all scalars, folded with point_add"""
+    points, sc, _ = inputs
+    n = len(sc)
+    S = pack(sc).reshape(n, 32)
+    prod = {k: oracle.mul_var_base(np.tile(pack([p]), n), S) for k, p in points.items()}
+    want = {}
+    for name, tbls in CASES.items():
+        acc = pack([(0, 1)] * n).reshape(n, 64)
+        for j, k in enumerate(tbls):
+            idx = [(i + 7 * j) % n for i in range(n)]
+            acc = oracle.point_add(acc, prod[k][idx])
+        want[name] = unpack(acc, 2)
+    return want
+
+
+def _check_output(out, inputs, expected):
+    points, sc, _ = inputs
+    lines = out.split("\n")
+    facts = {}
+    for l in lines:
+        f = l.split()
+        if f and f[0] in ("check", "entry", "anchor", "corrupt"):
+            facts.setdefault(f[0], []).append((int(f[1]), int(f[2])))
+    assert sorted(set(facts["check"])) == [(i, 0) for i in range(5)] and len(facts["check"]) == 6    # table 1 again after the repair
+    assert sorted(facts["entry"]) == [(i, 0) for i in range(5)]
+    assert all(bad > 0 for _, bad in facts["anchor"]) and len(facts["anchor"]) == 2
+    assert facts["corrupt"][0][0] == 1 and facts["corrupt"][0][1] > 0
+    got = {}
+    for l in lines:
+        f = l.split()
+        if f and f[0] == "r":
+            got.setdefault(f[1], []).append((int(f[2]), (int(f[3], 16), int(f[4], 16))))
+    assert sorted(got) == sorted(CASES)
+    for name in CASES:
+        assert [i for i, _ in got[name]] == list(range(len(sc))), name
+        for i, xy in got[name]:
+            assert xy == expected[name][i], (name, i, hex(sc[i]))
+
+
+def test_window_counts_and_patterns():
+    from bases_cases import ORDER8, base_windows, pattern
+    assert [base_windows(W) for W in (4, 5, 12, 16, 23, 28)] == [64, 51, 22, 16, 12, 10]
+    assert ORDER8 < 1 << 254
+    for W in (4, 5, 12, 16):
+        for d in (1 << (W - 1), (1 << (W - 1)) + 1):
+            v = pattern(W, d)
+            assert v < ORDER8 and v & ((1 << W) - 1) == d and v >> (W * (base_windows(W) - 3)) != 0
+
+
+def test_tables_and_results_match_the_oracle(inputs, expected, tmp_path):
+    exe = os.path.join(ROOT, "tests", "bases_emul", "bases_emul")
+    c = _build(exe, False)
+    assert c is None or c.returncode == 0, c.stdout
+    r = subprocess.run([exe], input=inputs[2], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    _check_output(r.stdout, inputs, expected)
+
+
+def test_the_same_program_under_asan_and_ubsan(inputs, expected):
+    for rt in ("libasan.so", "libubsan.so"):     # asked of the toolchain BEFORE the build: a build that fails is a failure
+        path = subprocess.run(["g++", "-print-file-name=" + rt], stdout=subprocess.PIPE, text=True).stdout.strip()
+        if not os.path.isabs(path) or not os.path.exists(path):
+            pytest.skip("no %s in this toolchain" % rt)
+    exe = os.path.join(ROOT, "tests", "bases_emul", "bases_emul_san")
+    c = _build(exe, True)
+    assert c is None or c.returncode == 0, c.stdout
+    r = subprocess.run([exe], input=inputs[2], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=1200,
+                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1"))
+    assert r.returncode == 0, r.stdout[-3000:]
+    assert "AddressSanitizer" not in r.stdout and "runtime error" not in r.stdout, r.stdout[-3000:]
+    _check_output(r.stdout, inputs, expected)
