@@ -51,6 +51,8 @@ EXT_SYMBOLS = ("bjj_msm_batch", "bjj_msm_batch_dev")
 # ... and include/bjj_hip_bases.h
 BASES_SYMBOLS = ("bjj_base_create", "bjj_base_free", "bjj_base_info", "bjj_base_check", "bjj_mul_bases", "bjj_mul_bases_dev")
 BJJ_MAX_BASES = 8
+# ... and include/bjj_hip_signer.h
+SIGNER_SYMBOLS = ("bjj_eddsa_verify_signer", "bjj_eddsa_verify_signer_dev", "bjj_schnorr_verify_signer", "bjj_schnorr_verify_signer_dev")
 
 
 class BjjInfo(ctypes.Structure):
@@ -191,6 +193,10 @@ def load():
     lib.bjj_base_check.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_uint64)]
     lib.bjj_mul_bases.argtypes = [vp, ctypes.POINTER(vp), ci, ctypes.POINTER(vp), sz, vp]
     lib.bjj_mul_bases_dev.argtypes = [vp, ctypes.POINTER(vp), ci, ctypes.POINTER(vp), sz, vp, vp]
+    lib.bjj_eddsa_verify_signer.argtypes = [vp, vp, vp, vp, vp, sz, vp]
+    lib.bjj_eddsa_verify_signer_dev.argtypes = [vp, vp, vp, vp, vp, sz, vp, vp]
+    lib.bjj_schnorr_verify_signer.argtypes = [vp, vp, vp, vp, vp, sz, vp]
+    lib.bjj_schnorr_verify_signer_dev.argtypes = [vp, vp, vp, vp, vp, sz, vp, vp]
     # multi-GPU
     pd = ctypes.POINTER(ctypes.c_double)
     lib.bjj_multi_init.argtypes = [ctypes.POINTER(ci), ci, ci, ctypes.POINTER(vp)]

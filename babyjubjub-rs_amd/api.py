@@ -349,6 +349,41 @@ class Context:
         hb, hs = self._base_args(list(bases), [int(p) for p in d_scalars], "mul_bases_dev")
         self._ck(self.lib.bjj_mul_bases_dev(self.handle, hb, len(d_scalars), hs, n, d_out, stream), "bjj_mul_bases_dev")
 
+    # ---- verification against one signer's table (include/bjj_hip_signer.h) ----
+    def _signer_handle(self, base, what):
+        if not isinstance(base, FixedBase) or base.ctx is not self or not base.handle:
+            raise BjjError("%s: the signer is a live FixedBase of this context" % what)
+        return base.handle.value
+
+    def _verify_signer(self, fn, name, base, r, s, msg):
+        h = self._signer_handle(base, name)
+        rr = _as_u8(r, 64, "r")
+        sv = _as_u8(s, 32, "s")
+        m = _as_u8(msg, 32, "msg")
+        n = sv.size // 32
+        if rr.size != n * 64 or m.size != n * 32:
+            raise BjjError("%s: array lengths disagree" % name)
+        ok = np.empty(n, dtype=np.uint8)
+        self._ck(fn(self.handle, h, rr.ctypes.data, sv.ctypes.data, m.ctypes.data, n, ok.ctypes.data), "bjj_" + name)
+        return ok
+
+    def eddsa_verify_signer(self, base, r_b8, s, msg):
+        """eddsa_verify for the ONE public key whose table `base` (a FixedBase of this context) holds: the same bytes as
+        eddsa_verify with that key repeated, from table gathers alone (bjj_eddsa_verify_signer).  -> (n,) uint8"""
+        return self._verify_signer(self.lib.bjj_eddsa_verify_signer, "eddsa_verify_signer", base, r_b8, s, msg)
+
+    def schnorr_verify_signer(self, base, r, s, msg):
+        """schnorr_verify for the one public key of `base`: 1 / 0 = Ok(true / false), 2 = Err (msg > Q)"""
+        return self._verify_signer(self.lib.bjj_schnorr_verify_signer, "schnorr_verify_signer", base, r, s, msg)
+
+    def eddsa_verify_signer_dev(self, base, d_r, d_s, d_msg, n, d_ok, stream=0):
+        self._ck(self.lib.bjj_eddsa_verify_signer_dev(self.handle, self._signer_handle(base, "eddsa_verify_signer_dev"), d_r, d_s, d_msg, n,
+                                                      d_ok, stream), "bjj_eddsa_verify_signer_dev")
+
+    def schnorr_verify_signer_dev(self, base, d_r, d_s, d_msg, n, d_ok, stream=0):
+        self._ck(self.lib.bjj_schnorr_verify_signer_dev(self.handle, self._signer_handle(base, "schnorr_verify_signer_dev"), d_r, d_s, d_msg,
+                                                        n, d_ok, stream), "bjj_schnorr_verify_signer_dev")
+
     def set_signer_constant_time(self, on=True):
         """signer hardening: public_keys / sign / sign_schnorr scan a small 4-bit table instead of indexing the big one
         with secret digits -- no secret-dependent address or branch; bit-identical results, ~2x slower sign"""
@@ -552,6 +587,14 @@ class FixedBase:
     def mul(self, scalars):
         """scalars[i] * P for every i -> (n, 64): Context.mul_bases with this one base"""
         return self.ctx.mul_bases([self], [scalars])
+
+    def verify(self, r_b8, s, msg):
+        """EdDSA-Poseidon signatures (R, s) over msg under THIS point as the public key -> (n,) uint8 (Context.eddsa_verify_signer)"""
+        return self.ctx.eddsa_verify_signer(self, r_b8, s, msg)
+
+    def verify_schnorr(self, r, s, msg):
+        """Schnorr signatures under this point as the public key -> (n,) uint8, 2 = Err (Context.schnorr_verify_signer)"""
+        return self.ctx.schnorr_verify_signer(self, r, s, msg)
 
 
 class MultiContext:

@@ -38,8 +38,10 @@
 #include "../../include/bjj_hip.h"
 #include "../../include/bjj_hip_msm_batch.h"
 #include "../../include/bjj_hip_bases.h"
+#include "../../include/bjj_hip_signer.h"
 #include "bjj_device.hpp"
 #include "bases.hpp"
+#include "signer.hpp"
 #include "bjj_launch.hpp"
 #include "msm.hpp"
 #include "copy_pool.hpp"
@@ -190,6 +192,7 @@ struct bjj_ctx {
   int lanes_fixed = 512, lanes_var = 512;
   int lanes_fixed_2x256 = 512;   // resident lanes per CU of K1's two-workgroup shape
   int lanes_bases = 512;         // resident lanes per CU of bjj_k_mul_bases
+  int lanes_signer = 512;        // resident lanes per CU of the bjj_k_*_verify_signer kernels
   std::vector<bjj_base*> user_bases;   // the tables bjj_base_create made and bjj_base_free has not released yet
   int verify_mode = -1;          // -1 = per call (persistent waves for one launch > 2^21 items that runs alone, groups otherwise), 0 / 1 = forced (BJJ_VERIFY_DISPATCH)
   int k2_variant = -1;           // -1 = per call (tiles for a launch that runs alone, grid-strided while another is in flight), 0 / 1 = forced (BJJ_K2_VARIANT)
@@ -1109,6 +1112,7 @@ int bjj_init(int device, int window_bits, bjj_ctx** out_ctx) {
   c->lanes_fixed = bjjk::fixed_base_lanes_per_cu(0);
   c->lanes_fixed_2x256 = bjjk::fixed_base_lanes_per_cu(1);
   c->lanes_bases = bjjk::bases_lanes_per_cu();
+  c->lanes_signer = bjjk::signer_lanes_per_cu();
   if (const char* e = getenv("BJJ_VERIFY_DISPATCH")) {
     if (e[0] == '0' || e[0] == '1') c->verify_mode = e[0] - '0';
   }
@@ -2408,6 +2412,74 @@ int bjj_mul_bases(bjj_ctx* c, const bjj_base* const* bases, int t, const uint8_t
   { int rc = set_leave(c, S, st); if (rc) return rc; }
   HIPCK(hipStreamSynchronize(st));
   return BJJ_OK;
+}
+
+// ---- verification against one signer's table (include/bjj_hip_signer.h) ------------------------------------------------------
+// argument checks of both forms; fills the two table descriptors (the signer's table: mod 8l; the context's B8 table: mod l)
+static int verify_signer_check(bjj_ctx* c, const bjj_base* signer, size_t n, const char* who, SignerArgs* A) {
+  if (!c) return set_err(BJJ_E_INVALID, std::string(who) + ": ctx is NULL");
+  if (!signer) return set_err(BJJ_E_INVALID, std::string(who) + ": signer is NULL");
+  if (!base_of_ctx(c, signer)) return set_err(BJJ_E_INVALID, std::string(who) + ": signer is not a base of this context");
+  CHECK_N(n);
+  memset(A, 0, sizeof(*A));
+  A->T.table = signer->table.p; A->T.W = signer->W; A->T.nwin = signer->nwin; A->T.mod_l = 0;
+  A->L.table = c->table.p; A->L.W = c->W; A->L.nwin = c->nwin; A->L.mod_l = 1;
+  A->pk = signer_point(signer->xy);
+  return BJJ_OK;
+}
+// No scratch set: the kernel keeps everything in registers and LDS, so calls on different streams share nothing.
+static int verify_signer_dev(bjj_ctx* c, bool schnorr, const bjj_base* signer, const void* d_r, const void* d_s, const void* d_msg, size_t n,
+                             void* d_ok, void* stream, const char* who) {
+  SignerArgs A;
+  { int rc = verify_signer_check(c, signer, n, who, &A); if (rc) return rc; }
+  if (n == 0) return BJJ_OK;
+  if (!d_r || !d_s || !d_msg || !aligned16(d_r) || !aligned16(d_s) || !aligned16(d_msg))
+    return set_err(BJJ_E_INVALID, std::string(who) + ": NULL or not 16-byte aligned device pointer");
+  if (!d_ok) return set_err(BJJ_E_INVALID, std::string(who) + ": d_ok is NULL");
+  DEV_ENTER(c, stream);
+  LAUNCHCK_S(bjjk::verify_signer(st, c->cus, c->lanes_signer, schnorr, A, (const uint8_t*)d_r, (const uint8_t*)d_s, (const uint8_t*)d_msg, n,
+                                 (uint8_t*)d_ok), who);
+  DEV_LEAVE(c);
+}
+// Synchronous: the three arrays go to the set's block with one copy each (pinned or pageable), one launch, one copy out.
+static int verify_signer_host(bjj_ctx* c, bool schnorr, const bjj_base* signer, const uint8_t* r, const uint8_t* s, const uint8_t* msg, size_t n,
+                              uint8_t* ok, const char* who) {
+  SignerArgs A;
+  { int rc = verify_signer_check(c, signer, n, who, &A); if (rc) return rc; }
+  if (n == 0) return BJJ_OK;
+  if (!r || !s || !msg || !ok) return set_err(BJJ_E_INVALID, std::string(who) + ": NULL buffer");
+  hipStream_t st = c->stream;
+  ENTER_DEVICE(c->device);
+  ScratchSet* S = pick_set(c, st);
+  const size_t o_s = up256(n * 64), o_msg = o_s + up256(n * 32), o_ok = o_msg + up256(n * 32);
+  if (S->bases_io.grow(o_ok + n) != hipSuccess) {
+    (void)hipGetLastError();
+    return set_err(BJJ_E_NOMEM, std::string(who) + ": cannot allocate " + std::to_string((o_ok + n) >> 20) + " MB of device staging");
+  }
+  { int rc = set_enter(c, S, st); if (rc) return rc; }
+  uint8_t* blk = S->bases_io;
+  HIPCK(hipMemcpyAsync(blk, r, n * 64, hipMemcpyHostToDevice, st));
+  HIPCK(hipMemcpyAsync(blk + o_s, s, n * 32, hipMemcpyHostToDevice, st));
+  HIPCK(hipMemcpyAsync(blk + o_msg, msg, n * 32, hipMemcpyHostToDevice, st));
+  LAUNCHCK_S(bjjk::verify_signer(st, c->cus, c->lanes_signer, schnorr, A, blk, blk + o_s, blk + o_msg, n, blk + o_ok), who);
+  HIPCK(hipMemcpyAsync(ok, blk + o_ok, n, hipMemcpyDeviceToHost, st));
+  { int rc = set_leave(c, S, st); if (rc) return rc; }
+  HIPCK(hipStreamSynchronize(st));
+  return BJJ_OK;
+}
+int bjj_eddsa_verify_signer(bjj_ctx* c, const bjj_base* signer, const uint8_t* r_xy, const uint8_t* s, const uint8_t* msg, size_t n, uint8_t* ok) {
+  return verify_signer_host(c, false, signer, r_xy, s, msg, n, ok, "bjj_eddsa_verify_signer");
+}
+int bjj_eddsa_verify_signer_dev(bjj_ctx* c, const bjj_base* signer, const void* d_r_xy, const void* d_s, const void* d_msg, size_t n, void* d_ok,
+                                void* stream) {
+  return verify_signer_dev(c, false, signer, d_r_xy, d_s, d_msg, n, d_ok, stream, "bjj_eddsa_verify_signer_dev");
+}
+int bjj_schnorr_verify_signer(bjj_ctx* c, const bjj_base* signer, const uint8_t* r_xy, const uint8_t* s, const uint8_t* msg, size_t n, uint8_t* ok) {
+  return verify_signer_host(c, true, signer, r_xy, s, msg, n, ok, "bjj_schnorr_verify_signer");
+}
+int bjj_schnorr_verify_signer_dev(bjj_ctx* c, const bjj_base* signer, const void* d_r_xy, const void* d_s, const void* d_msg, size_t n, void* d_ok,
+                                  void* stream) {
+  return verify_signer_dev(c, true, signer, d_r_xy, d_s, d_msg, n, d_ok, stream, "bjj_schnorr_verify_signer_dev");
 }
 
 #pragma GCC visibility pop

@@ -18,6 +18,7 @@
 #endif
 
 namespace bjj { struct BasesArgs; }   // bases.hpp: the per-base descriptors of bjj_k_mul_bases
+namespace bjj { struct SignerArgs; }  // signer.hpp: the two tables and the point of bjj_k_verify_signer
 
 namespace bjjk {
 
@@ -135,5 +136,11 @@ hipError_t base_window_bases(hipStream_t st, uint32_t* bases, int W, int nwin, c
 hipError_t check_base_table(hipStream_t st, int grid, const uint32_t* table, const uint32_t* bases, int W, int nwin, const uint32_t xy[16],
                             unsigned long long* d_bad);
 hipError_t mul_bases(hipStream_t st, int cus, int lanes_per_cu, const bjj::BasesArgs& A, size_t n, uint8_t* out, uint32_t* scratch);
+
+// k_signer.hip: verify / verify_schnorr against the one public key whose table A.T is (one item per lane, 256-lane workgroups,
+// no scratch): ok[i] = 0 / 1, with schnorr 0 / 1 / 2
+int signer_lanes_per_cu();
+hipError_t verify_signer(hipStream_t st, int cus, int lanes_per_cu, bool schnorr, const bjj::SignerArgs& A, const uint8_t* r, const uint8_t* s,
+                         const uint8_t* msg, size_t n, uint8_t* ok);
 
 }  // namespace bjjk
