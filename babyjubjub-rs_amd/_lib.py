@@ -84,6 +84,7 @@ class BjjInfo(ctypes.Structure):
         ("last_poseidon_form", ctypes.c_int),
         ("last_sign_form", ctypes.c_int),
         ("table_alloc", ctypes.c_int),
+        ("last_fixed_base_slots", ctypes.c_int),
     ]
 
 

@@ -139,6 +139,11 @@ static size_t list_bytes(size_t n) { return (n + 16) * sizeof(u32); }
 
 #define BJJ_PIPE_BUFS 4
 #define BJJ_SCRATCH_SETS 2
+// K1's two-workgroup shape on device pointers: workgroup slots per CU one launch takes (2 = 512 workgroups of 8 items per lane at 2^20
+// items, 1 = 256 of 16; profiles/r09_ab_k1_long_lanes.txt)
+#ifndef BJJ_K1_OVERLAP_SLOTS_DEFAULT
+#define BJJ_K1_OVERLAP_SLOTS_DEFAULT 1
+#endif
 #define BJJ_STREAM_MARKS 8
 struct ScratchSet {
   DevBlock<u32> scratch;       // n * 64 B (Z, prefix)
@@ -197,6 +202,8 @@ struct bjj_ctx {
   int verify_mode = -1;          // -1 = per call (persistent waves for one launch > 2^21 items that runs alone, groups otherwise), 0 / 1 = forced (BJJ_VERIFY_DISPATCH)
   int k2_variant = -1;           // -1 = per call (tiles for a launch that runs alone, grid-strided while another is in flight), 0 / 1 = forced (BJJ_K2_VARIANT)
   int k1_variant = -1;           // -1 = per call (two-workgroup shape while another launch of the context is in flight), 0 / 1 = forced (BJJ_K1_VARIANT)
+  int k1_overlap_slots = BJJ_K1_OVERLAP_SLOTS_DEFAULT;   // workgroup slots per CU a launch of the two-workgroup shape takes (BJJ_K1_OVERLAP_SLOTS = 1 | 2)
+  int last_k1_slots = -1;
   int occ_poseidon = 1, occ_verify = 1, occ_scan = 1, occ_add = 1;
   // Variable base, off-curve points (k_var.hip): K6 runs BEHIND K2 on the caller's stream (nothing extra for a clean batch) or,
   // with the list made by a scan, BESIDE it on the set's priority stream.  -1 = per call by what the previous calls met
@@ -354,10 +361,15 @@ static int fixed_base_variant(bjj_ctx* c, const ScratchSet* S) {
   c->last_k1 = kv;
   return kv;
 }
-// lanes per CU the launch may take: everything its shape can hold, or -- chunk launches of a host-pointer call, PipeSpec::k1_half --
-// one 256-lane workgroup per CU, so that the neighbouring chunk's launch has the other slot
-static int fixed_base_lanes(const bjj_ctx* c, int kv) {
-  if (c->k1_half_now && kv == 1) return 256;
+// lanes per CU the launch may take: everything its shape can hold, or ONE 256-lane workgroup per CU, so that the neighbouring
+// launch has the other slot and every lane keeps its slot for the whole launch (one ramp, one running product, one inversion
+// per slot instead of two) -- always for the chunk launches of a host-pointer call (PipeSpec::k1_half), and for launches on
+// device pointers that get the two-workgroup shape when the context's k1_overlap_slots is 1.  The shape is only ever chosen for
+// a launch that shares the chip (expect_overlap) or forced (BJJ_K1_VARIANT=1): a launch that runs alone keeps the 512-lane form.
+static int fixed_base_lanes(bjj_ctx* c, int kv) {
+  const bool one_slot = kv == 1 && (c->k1_half_now || c->k1_overlap_slots == 1);
+  c->last_k1_slots = kv == 1 ? (one_slot ? 1 : 2) : 0;
+  if (one_slot) return 256;
   return kv ? c->lanes_fixed_2x256 : c->lanes_fixed;
 }
 // completion mark of a call that used no scratch (bjj_sync waits for these)
@@ -1142,6 +1154,9 @@ int bjj_init(int device, int window_bits, bjj_ctx** out_ctx) {
   if (const char* e = getenv("BJJ_K1_VARIANT")) {   // tests / A-B: force one shape of the fixed-base kernel
     if (e[0] == '0' || e[0] == '1') c->k1_variant = e[0] - '0';
   }
+  if (const char* e = getenv("BJJ_K1_OVERLAP_SLOTS")) {   // tests / A-B: workgroup slots per CU of a two-workgroup-shape launch on device pointers
+    if (e[0] == '1' || e[0] == '2') c->k1_overlap_slots = e[0] - '0';
+  }
   if (const char* e = getenv("BJJ_VB_SPLIT")) {     // tests / A-B: K6 always behind K2 (0) or always beside it, behind a scan (1)
     if (e[0] == '0' || e[0] == '1') c->vb_split = e[0] - '0';
   }
@@ -1341,6 +1356,7 @@ int bjj_get_info(bjj_ctx* c, bjj_info* out) {
   info->kernel_fixed_base_overlap = "bjj_k_mul_fixed_base_2x256";   // the forms overlapping launches get (expect_overlap)
   info->kernel_var_base_overlap = "bjj_k_mul_var_base";
   info->table_alloc = c->table_alloc;
+  info->last_fixed_base_slots = c->last_k1_slots;
   const size_t fill = cap < sizeof(full) ? cap : sizeof(full);   // never past the caller's struct
   full.struct_size = (uint32_t)fill;
   memcpy(out, &full, fill);
@@ -1414,7 +1430,7 @@ static int fixed_base_launch(bjj_ctx* c, const void* d_scalars, size_t n, void* 
     return set_err(BJJ_E_INVALID, std::string(who) + ": NULL or not 16-byte aligned device pointer");
   if (n <= c->fb_quad_max && c->k1_variant < 0) {   // short calls (a single B8.mul_scalar is one): four lanes per item, no scratch (k_small.hip)
     DEV_ENTER(c, stream);
-    c->last_k1 = 2;
+    c->last_k1 = 2; c->last_k1_slots = 0;
     LAUNCHCK_S(bjjk::mul_fixed_base_quad(st, c->table, c->W, c->nwin, (const uint8_t*)d_scalars, n, (uint8_t*)d_out, compressed), who);
     DEV_LEAVE(c);
   }
@@ -1914,7 +1930,7 @@ static int public_keys_launch(bjj_ctx* c, const void* d_keys, size_t n, void* d_
     LAUNCHCK(bjjk::mul_fixed_base_scan(st, c->cus, c->ct_table, BJJ_CT_W, fixed_nwin(BJJ_CT_W), S->codec, n, (uint8_t*)d_out_xy, S->scratch, xy),
              "mul_fixed_base_scan");
   } else if (n <= c->fb_quad_max && c->k1_variant < 0) {   // short calls: four lanes per key (k_small.hip)
-    c->last_k1 = 2;
+    c->last_k1 = 2; c->last_k1_slots = 0;
     LAUNCHCK(bjjk::mul_fixed_base_quad(st, c->table, c->W, c->nwin, S->codec, n, (uint8_t*)d_out_xy, compressed), "mul_fixed_base (short call)");
   } else {
     const int kv = fixed_base_variant(c, S);

@@ -84,6 +84,11 @@ __device__ __forceinline__ void mul_fixed_base_body(const u32* __restrict__ tabl
 //    two run half a period out of phase, and one launch's serial section -- the inversion by one wave while the other waves of
 //    its workgroup wait, then the epilogue -- is covered by the other launch's main loop: 1.84 vs 1.75 G mults/s on two streams
 //    (profiles/r03_ab_k1_2x256_two_streams.txt).  The host picks the shape per call (bjj_hip.hip: fixed_base_variant).
+//    Its grid is ONE workgroup per CU (bjj_hip.hip: fixed_base_lanes): the launch asks only for the slot it would get anyway, so a
+//    lane keeps its slot for all of its items -- 16 at 2^20 items on 256 CUs -- and a slot runs one ramp, one running product
+//    and one inversion per launch instead of two: +2.3 ... 2.5 % on two streams over the grid of two workgroups per CU, whose
+//    second workgroup on every slot repeated all three (profiles/r09_ab_k1_long_lanes.txt; BJJ_K1_OVERLAP_SLOTS=2 gives that
+//    grid back).  The kernel is grid-strided and its stash is indexed by item, so the grid is the host's business alone.
 __global__ void __launch_bounds__(BJJ_K1_BLOCK, BJJ_K1_MIN_BLOCKS) bjj_k_mul_fixed_base(const u32* __restrict__ table, int W, int nwin,
                                                                   const uint8_t* __restrict__ scalars, size_t n,
                                                                   uint8_t* __restrict__ out, u32* __restrict__ scratch) {

@@ -80,7 +80,9 @@
  * Environment knobs (read by bjj_init; for tests and A/B runs): BJJ_K1_VARIANT,
  * BJJ_K2_VARIANT, BJJ_VERIFY_DISPATCH = 0 | 1 force one form of the fixed-base /
  * variable-base / verify kernel instead of the per-call choice; BJJ_VB_SPLIT = 0 | 1
- * forces where the exact kernel of the variable-base path runs (below).
+ * forces where the exact kernel of the variable-base path runs (below);
+ * BJJ_K1_OVERLAP_SLOTS = 1 | 2: workgroup slots per CU that a fixed-base launch of
+ * the overlap form takes on device pointers (bjj_info.last_fixed_base_slots).
  *
  * Malformed points on the variable-base path.  Point has pub fields and no check (src/lib.rs:134-138), so an
  * (x, y) that is not on the curve is a legal input; its result is whatever the reference's formula sequence
@@ -366,6 +368,8 @@ typedef struct {
   int last_sign_form;          /* bjj_sign / bjj_sign_compressed: 0 = one signature per lane, 1 = eight lanes per signature (short calls) */
   int table_alloc;             /* the fixed-base table's memory, BJJ_TABLE_ALLOC_*: plain device memory (the default), uncached device memory
                                   (BJJ_TABLE_UNCACHED=1 in the environment of bjj_init), or plain after the uncached allocation failed */
+  int last_fixed_base_slots;   /* workgroup slots per CU the last fixed-base launch took: 1 or 2 for last_fixed_base_shape == 1 (one = every lane keeps
+                                  its slot for the whole launch; BJJ_K1_OVERLAP_SLOTS = 1 | 2 forces one), 0 for the other shapes */
 } bjj_info;
 int bjj_get_info(bjj_ctx* ctx, bjj_info* info);
 

@@ -44,6 +44,7 @@ pub struct BjjInfo {
     pub last_poseidon_form: c_int,
     pub last_sign_form: c_int,
     pub table_alloc: c_int,
+    pub last_fixed_base_slots: c_int,
 }
 
 pub const BJJ_OK: c_int = 0;
