@@ -1,4 +1,4 @@
-// copy_pool.hpp -- the worker threads of the host-pointer pipeline (bjj_hip.hip: run_pipelined).  Plain C++ (no HIP): also
+// copy_pool.hpp -- the worker threads of the host-pointer pipeline (host_pipe.inc: run_pipelined).  Plain C++ (no HIP): also
 // built for the CPU with ThreadSanitizer / AddressSanitizer by tests/test_emul_sanitizers.py (tests/emul/emul_copy_pool.cpp).
 #pragma once
 #include <stddef.h>

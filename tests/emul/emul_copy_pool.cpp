@@ -1,5 +1,5 @@
 // TEST INFRASTRUCTURE: the copy workers of the host-pointer pipeline (babyjubjub-rs_amd/csrc/copy_pool.hpp) driven the way
-// run_pipelined drives them -- copy-in groups one chunk ahead, copy-out groups harvested in order, a 4-deep ring of staging
+// run_pipelined (host_pipe.inc) drives them -- copy-in groups one chunk ahead, copy-out groups harvested in order, a 4-deep ring of staging
 // buffers that is recycled -- on the CPU, under ThreadSanitizer / AddressSanitizer (tests/test_emul_sanitizers.py).
 // Exit code 0 = every byte arrived; prints "copy_pool ok <bytes>".
 #include <stdio.h>

@@ -45,7 +45,7 @@ def test_c_oracle_under_asan_and_ubsan():
 
 @pytest.mark.parametrize("san", ["thread", "address,undefined"])
 def test_copy_workers_of_the_host_pipeline_under_tsan_and_asan(san, tmp_path):
-    """babyjubjub-rs_amd/csrc/copy_pool.hpp driven like run_pipelined drives it (groups one chunk ahead, ordered harvest, a
+    """babyjubjub-rs_amd/csrc/copy_pool.hpp driven like run_pipelined (host_pipe.inc) drives it (groups one chunk ahead, ordered harvest, a
     recycled 4-deep ring), with 1, 4 and 7 workers: no data race, no out-of-bounds slice, every byte delivered"""
     exe = str(tmp_path / "emul_copy_pool")
     src = os.path.join(ROOT, "tests", "emul", "emul_copy_pool.cpp")

@@ -8,6 +8,8 @@ import ctypes
 import numpy as np
 import pytest
 
+from pipe_model import schedule as _schedule
+
 pytestmark = pytest.mark.gpu
 
 
@@ -165,6 +167,48 @@ c.close()
     assert (got == oracle.mul_fixed_base(w.scalars_254(10000, offset=9))).all()
 
 
+def test_forced_chunk_sizes_and_lane_parity_from_the_environment(oracle):
+    """BJJ_PIPE_SCHEDULE / BJJ_PIPE_LANE_PARITY (developer knobs, read on the first host-pointer call of a process), in child
+    processes: 10 000 items on pinned memory in chunks of 1 024, 2 048 x 4 and the 784 that remain -- six chunks -- with the lanes
+    as the entry point has them and with either parity forced; the bytes do not change."""
+    import os
+    import subprocess
+    import sys
+    import tempfile
+    from conftest import ROOT
+    from babyjubjub_rs_amd import workload as w
+    code = r'''
+import numpy as np, sys
+sys.path.insert(0, %r)
+import babyjubjub_rs_amd as bjj
+from babyjubjub_rs_amd import workload as w
+c = bjj.Context(0, 16)
+n = 10000
+sc = np.ascontiguousarray(w.scalars_254(n, offset=9)).reshape(-1)
+p_in, p_out = c.host_empty(n * 32), c.host_empty(n * 64)
+p_in[:] = sc
+c._ck(c.lib.bjj_mul_fixed_base(c.handle, p_in.ctypes.data, n, p_out.ctypes.data), "fb")
+i = c.info()
+print("INFO", i.last_host_direct_arrays, i.last_host_staged_arrays, i.last_host_chunks)
+np.save(sys.argv[1], np.asarray(p_out).copy())
+c.close()
+''' % ROOT
+    want = oracle.mul_fixed_base(w.scalars_254(10000, offset=9))
+    base = {k: v for k, v in os.environ.items() if k != "BJJ_PIPE_LANE_PARITY"}
+    with tempfile.TemporaryDirectory() as td:
+        runs = []                                              # the three children side by side: each is mostly start-up
+        for parity in (None, "0", "1"):
+            env = dict(base, BJJ_PIPE_SCHEDULE="1024,2048", **({} if parity is None else {"BJJ_PIPE_LANE_PARITY": parity}))
+            outp = os.path.join(td, "out_%s.npy" % parity)
+            runs.append((parity, outp, subprocess.Popen([sys.executable, "-c", code, outp], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))
+        for parity, outp, proc in runs:
+            stdout, _ = proc.communicate(timeout=600)
+            assert proc.returncode == 0, (parity, stdout)
+            info = [l for l in stdout.splitlines() if l.startswith("INFO")][0].split()[1:]
+            assert [int(x) for x in info] == [2, 0, 6], (parity, stdout)
+            assert (np.load(outp).reshape(10000, 64) == want).all(), parity
+
+
 def test_every_host_entry_point_on_pinned_memory_equals_the_staged_path(ctx16, oracle):
     """The 16 host-pointer batch entry points with EVERY array in pinned memory (several inputs, up to three outputs, key material that
     is wiped behind the call) against the same call on pageable memory, 140 001 items = three chunks over both lanes; the
@@ -274,20 +318,6 @@ def _verify_one_launch(ctx, schnorr, pk, r, s, msg):
     f(d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), d[3].data_ptr(), n, d_ok.data_ptr(), 0)
     ctx.sync()
     return d_ok.cpu().numpy()
-
-
-def _schedule(n, first, cap_chunk):
-    """the chunk schedule of run_super_batch (bjj_hip.hip): first, doubling up to the cap, a remainder below half a chunk joins the last one"""
-    out, lo, sz = [], 0, first
-    while lo < n:
-        take = min(sz, n - lo)
-        if n - lo - take < sz // 2:
-            take = n - lo
-        out.append(take)
-        lo += take
-        if sz < cap_chunk:
-            sz = min(sz * 2, cap_chunk)
-    return out
 
 
 def test_super_batches_when_the_device_staging_budget_is_small(oracle):

@@ -1,0 +1,180 @@
+"""The plan of the host-pointer pipeline (babyjubjub-rs_amd/csrc/pipe_plan.hpp: chunk schedule, lane parity, staging and ring
+offsets, super-batch cap, the two knob parsers) as pure functions on the CPU: tests/emul/emul_pipe_plan.cpp, built with
+AddressSanitizer and UBSan and run directly, prints the plan of every case below; the cases are compared with the model of the
+schedule (pipe_model.py), with the layout computed here, and with the invariants every plan has."""
+import itertools
+import json
+import os
+import subprocess
+
+import pytest
+
+from conftest import ROOT
+from pipe_model import schedule
+
+STRIDES = (1, 32, 64, 96, 160)
+
+
+def case(n, first=0, cap=0, tail=0, in_strides=(32,), out_strides=(64,), in_direct=None, out_direct=None, extra=0, last_on_prio=0,
+         out_at_end=0, pipe_first=1 << 15, pipe_chunk=1 << 17, env=0, forced="-", parity=-1):
+    in_direct = in_direct if in_direct is not None else (1,) * len(in_strides)
+    out_direct = out_direct if out_direct is not None else (1,) * len(out_strides)
+    return dict(n=n, first=first, cap=cap, tail=tail, in_strides=in_strides, out_strides=out_strides, in_direct=in_direct, out_direct=out_direct,
+                extra=extra, last_on_prio=last_on_prio, out_at_end=out_at_end, pipe_first=pipe_first, pipe_chunk=pipe_chunk, env=env, forced=forced,
+                parity=parity)
+
+
+def _line(c):
+    csv = lambda v: ",".join(str(int(x)) for x in v)
+    return "plan %d %d %d %s %s %s %s %d %d %d %d %d %d %d %d %d %s %d" % (
+        c["n"], len(c["in_strides"]), len(c["out_strides"]), csv(c["in_strides"]), csv(c["out_strides"]), csv(c["in_direct"]), csv(c["out_direct"]),
+        c["extra"], c["first"], c["cap"], c["tail"], c["last_on_prio"], c["out_at_end"], c["pipe_first"], c["pipe_chunk"], c["env"], c["forced"],
+        c["parity"])
+
+
+@pytest.fixture(scope="module")
+def emul(tmp_path_factory):
+    """run(lines) -> the program's output lines; the sanitizers abort on the first finding"""
+    exe = str(tmp_path_factory.mktemp("pipe_plan") / "emul_pipe_plan")
+    src = os.path.join(ROOT, "tests", "emul", "emul_pipe_plan.cpp")
+    c = subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe, src],
+                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    if c.returncode != 0 and "sanitize" in c.stdout:
+        pytest.skip("sanitizer runtime not available: " + c.stdout[-300:])
+    assert c.returncode == 0, c.stdout
+
+    def run(lines):
+        r = subprocess.run([exe], input="\n".join(lines) + "\n", stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300,
+                           env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1"))
+        assert r.returncode == 0, r.stdout[-3000:]
+        assert "AddressSanitizer" not in r.stdout and "runtime error" not in r.stdout, r.stdout[-3000:]
+        out = r.stdout.splitlines()
+        assert len(out) == len(lines), r.stdout[-3000:]
+        return out
+    return run
+
+
+def up(v, a):
+    return (v + a - 1) // a * a
+
+
+def check_plan(c, p):
+    """what holds for every plan: the schedule's invariants and the whole layout, recomputed from the chunk sizes"""
+    n, lo = c["n"], p["lo_of"]
+    sizes = [b - a for a, b in zip(lo, lo[1:])]
+    assert lo[0] == 0 and lo[-1] == n and all(s > 0 for s in sizes) and p["nchunks"] == len(sizes), (c, p)
+    assert p["max_chunk"] == max(sizes), (c, p)
+    # device staging: inputs, outputs, the exact stage's bytes -- in this order, each at the next multiple of 256 behind the one before
+    at = 0
+    for off, stride in zip(p["d_in_off"] + p["d_out_off"] + [p["d_extra_off"]], list(c["in_strides"]) + list(c["out_strides"]) + [c["extra"]]):
+        assert off % 256 == 0 and off == at, (c, p)            # in order, no overlap, no hole of 256 bytes or more
+        at = up(off + n * stride, 256)
+    assert p["dev_tot"] == at, (c, p)                          # the end of the last device array
+    # pinned rings: only staged arrays take space, a slot holds max_chunk items (the whole array for outputs that leave at the end)
+    for offs, strides, direct, ring, items in ((p["r_in_off"], c["in_strides"], c["in_direct"], p["in_ring"], p["max_chunk"]),
+                                               (p["r_out_off"], c["out_strides"], c["out_direct"], p["out_ring"], n if c["out_at_end"] else p["max_chunk"])):
+        at = 0
+        for off, stride, d in zip(offs, strides, direct):
+            if not d:
+                assert off % 16 == 0 and off == at, (c, p)
+                at = up(off + items * stride, 16)
+        assert ring == at, (c, p)
+    return sizes
+
+
+def plans(emul, cases):
+    out = [json.loads(l) for l in emul([_line(c) for c in cases])]
+    return [check_plan(c, p) for c, p in zip(cases, out)], out
+
+
+def test_default_schedule_equals_the_model_for_every_size(emul):
+    for first, cap in ((64, 256), (64, 64)):
+        cases = [case(n, pipe_first=first, pipe_chunk=cap) for n in range(1, 6001)]
+        sizes, _ = plans(emul, cases)
+        assert sizes == [schedule(n, first, cap) for n in range(1, 6001)]
+        # ... and the same schedule when it is the entry point's own, over another one of the context
+        sizes, _ = plans(emul, [case(n, first=first, cap=cap) for n in range(1, 6001, 7)])
+        assert sizes == [schedule(n, first, cap) for n in range(1, 6001, 7)]
+
+
+def test_schedules_the_project_relies_on(emul):
+    sizes, _ = plans(emul, [case(10000, pipe_first=1024, pipe_chunk=2048, env=1), case(140001, pipe_first=1 << 15, pipe_chunk=1 << 18),
+                            case(140001, first=1 << 16, cap=1 << 19), case(140001, first=1 << 16, cap=1 << 18),
+                            case(140001, first=1 << 20, cap=1 << 18)])
+    assert sizes[0] == [1024, 2048, 2048, 2048, 2832]
+    assert sizes[1] == [32768, 65536, 41697]
+    assert sizes[2] == schedule(140001, 1 << 16, 1 << 19) == [65536, 74465]
+    assert sizes[3] == schedule(140001, 1 << 16, 1 << 18) == [65536, 74465]
+    assert sizes[4] == [140001]                                # a first chunk above the cap is the cap
+
+
+def test_tail_chunk(emul):
+    tail = 512
+    ns = [4 * tail - 1, 4 * tail, 4 * tail + 1, 10000, 65536 + 300]
+    with_tail, _ = plans(emul, [case(n, first=1024, cap=4096, tail=tail) for n in ns])
+    without, _ = plans(emul, [case(n, first=1024, cap=4096) for n in ns])
+    body, _ = plans(emul, [case(n - tail, first=1024, cap=4096) for n in ns])
+    for n, a, b, c in zip(ns, with_tail, without, body):
+        if n >= 4 * tail:
+            assert a == c + [tail], n                          # the last chunk is exactly the tail, the rest is scheduled as before
+        else:
+            assert a == b, n
+    # a schedule from the environment: first_chunk, max_chunk and tail_chunk of the entry point are ignored
+    env, _ = plans(emul, [case(n, first=1024, cap=4096, tail=tail, pipe_first=128, pipe_chunk=1024, env=1) for n in ns])
+    assert env == [schedule(n, 128, 1024) for n in ns]
+
+
+def test_forced_schedule(emul):
+    f = lambda n, s, **kw: case(n, first=1024, cap=4096, tail=512, forced=s, **kw)
+    sizes, _ = plans(emul, [f(10000, "1024,2048"), f(10000, "1030,2111"), f(10000, "63,1024,10,2048,0"), f(100, "1024,2048"), f(3072, "1024,2048"),
+                            f(10000, "63,10"), f(10000, "-"), f(10000, "1024,2048", env=1)])
+    assert sizes[0] == [1024, 2048, 2048, 2048, 2048, 784]     # the last size repeats; what remains is a short chunk of its own
+    assert sizes[1] == [1024, 2048, 2048, 2048, 2048, 784]     # sizes are rounded down to a multiple of 64
+    assert sizes[2] == sizes[0]                                # entries below 64 are dropped
+    assert sizes[3] == [100] and sizes[4] == [1024, 2048]
+    assert sizes[5] == sizes[6] == schedule(10000 - 512, 1024, 4096) + [512]   # an empty list is no override
+    assert sizes[7] == sizes[0]
+    assert emul(["sched 1024,2048", "sched", "sched 63,64,0x80,130", "sched 100;7", "sched x"]) == \
+        ['"sched":[1024,2048]', '"sched":[]', '"sched":[64,128,128]', '"sched":[64]', '"sched":[]']
+
+
+def test_lane_parity(emul):
+    ns = [64 * k for k in range(1, 10)]                        # 1 .. 9 chunks of 64 items
+    cases = [case(n, pipe_first=64, pipe_chunk=64, last_on_prio=lp, parity=par) for n in ns for lp in (0, 1) for par in (-1, 0, 1)]
+    sizes, out = plans(emul, cases)
+    for c, s, p in zip(cases, sizes, out):
+        assert len(s) == c["n"] // 64
+        if c["parity"] >= 0:
+            assert p["lane_flip"] == c["parity"]               # the override wins
+        elif c["last_on_prio"]:
+            assert (len(s) - 1 + p["lane_flip"]) & 1 == 1      # the last chunk runs on lane 1, the priority stream
+        else:
+            assert p["lane_flip"] == 0
+
+
+def test_layout_of_device_staging_and_pinned_rings(emul):
+    """1 to 4 inputs and outputs, every mix of pinned (direct) and pageable (staged) arrays, strides that rotate through the set;
+    check_plan recomputes every offset"""
+    cases = []
+    for n_in, n_out in itertools.product(range(1, 5), repeat=2):
+        for k, mask in enumerate(itertools.product((0, 1), repeat=n_in + n_out)):
+            strides = [STRIDES[(k + 2 * i + n_in) % len(STRIDES)] for i in range(n_in + n_out)]
+            cases.append(case(4097 + k, in_strides=strides[:n_in], out_strides=strides[n_in:], in_direct=mask[:n_in], out_direct=mask[n_in:],
+                              extra=(0, 162)[k & 1], out_at_end=(k >> 1) & 1, pipe_first=1024, pipe_chunk=2048))
+    assert len(cases) == 900
+    sizes, out = plans(emul, cases)
+    for c, p in zip(cases, out):
+        assert (p["in_ring"] == 0) == all(c["in_direct"]) and (p["out_ring"] == 0) == all(c["out_direct"])
+    assert {s for c in cases for s in c["in_strides"]} == set(STRIDES) == {s for c in cases for s in c["out_strides"]}
+
+
+def test_super_batch_cap(emul):
+    assert emul(["cap %d 96 2048" % (1 << 20), "cap 1000 96 2048", "cap %d 96 2048" % (96 * 2048), "cap %d 96 2048" % (96 * 4096 - 1),
+                 "cap %d 193 2048" % (1 << 20)]) == ["10240", "2048", "2048", "2048", "4096"]
+    assert -(-50000 // 10240) == 5                             # test_super_batches_when_the_device_staging_budget_is_small
+
+
+def test_items_knob_parser(emul):
+    got = emul(["items 777 NULL", "items 777", "items 777 63", "items 777 64", "items 777 65", "items 777 2048", "items 777 %d" % (1 << 24),
+                "items 777 %d" % ((1 << 24) + 1), "items 777 0x1000", "items 777 abc", "items 777 -5"])
+    assert got == ["777", "777", "777", "64", "128", "2048", str(1 << 24), "777", "4096", "777", "777"]

@@ -1,4 +1,4 @@
-// Developer probe for the host-pointer pipeline (bjj_hip.hip: run_pipelined): (1) raw PCIe copy rates per flavour of pinned
+// Developer probe for the host-pointer pipeline (host_pipe.inc: run_pipelined): (1) raw PCIe copy rates per flavour of pinned
 // memory and per copy size, (2) bjj_mul_fixed_base / bjj_eddsa_verify on each flavour of caller memory.
 //   hipcc -O2 -o host_pipe_probe host_pipe_probe.cpp -I../../include -L../../babyjubjub-rs_amd/csrc -lbjj_hip -Wl,-rpath,'$ORIGIN/../../babyjubjub-rs_amd/csrc'
 //   ./host_pipe_probe [window_bits=23] [calls=5] [what=all|fb_pinned|fb_pageable|v_pinned]
