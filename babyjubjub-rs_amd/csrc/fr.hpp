@@ -264,8 +264,8 @@ BJJ_HD Fr fr_sqr(const Fr& a) {
   return r;
 }
 
-// value-preserving (mod r) weak reduction of an N-form value: result < r + 2^233.
-// q = floor(top limb / (floor(r / 2^232) + 1)) never exceeds floor(x / r).
+// value-preserving (mod r) weak reduction of an N-form value (top limb < 2^26): result < r + (q + 1) * 2^232, and so < 2r
+// (q <= 21).  q = floor(top limb / (floor(r / 2^232) + 1)) never exceeds floor(x / r).
 BJJ_HD Fr fr_reduce_weak(const Fr& x) {
   const u32 q = x.v[8] / 3171407u;  // floor(r / 2^232) = 0x30644e = 3171406
   Fr r;

@@ -1,0 +1,28 @@
+// DEBUG HARNESS (tests only): the dispatcher of tests/devfuzz/field_ops.hpp -- the shipped field layer, square root and codec
+// items on raw limbs or words -- built by g++ with the bound assertions of csrc/fr.hpp live (the BJJ_ASSERTs of fr_sub,
+// fr_sub8, fr_sub_lazy, fr_sub8_of_lazy and the operand checks of fr_mul).  tests/test_field_ops_host.py checks it against
+// plain integers; tests/test_gpu_field_ops.py compares the device build with it bit for bit.  Not a fallback, not linked into
+// libbjj_hip.so.
+#define BJJ_DEBUG_BOUNDS 1
+#include <stddef.h>
+#include <stdint.h>
+#include "../../babyjubjub-rs_amd/csrc/bjj_device.hpp"
+#include "../../babyjubjub-rs_amd/csrc/bjj_constants.inc"
+#include "../devfuzz/field_ops.hpp"
+using namespace bjj;
+static const Consts K = {
+    BJJ_K_A, BJJ_K_D, BJJ_K_F, BJJ_K_FINV_PLAIN, BJJ_K_FINV, BJJ_K_L_R1, BJJ_K_L_R2, BJJ_K_DP, BJJ_K_D2P, BJJ_K_DPINV, BJJ_K_B8X, BJJ_K_B8Y, BJJ_K_TS_G, BJJ_K_HALFQ,
+    BJJ_K_ORDER, BJJ_K_ORDER2, BJJ_K_ORDER4, BJJ_K_L, BJJ_K_L2, BJJ_K_L4,
+    BJJ_K_POSEIDON_CF, BJJ_K_POSEIDON_KP, BJJ_K_POSEIDON_SP, BJJ_K_POSEIDON_AL, BJJ_K_POSEIDON_M, BJJ_K_POSEIDON_CAB,
+    BJJ_K_TS_NEG, BJJ_K_TS_HALF, BJJ_K_TS_HASH};
+
+// a: n records of field_words(op, 0) words, b: n records of field_words(op, 1) (may be null when 0), out: n of field_words(op, 2)
+extern "C" int emul_field_op(int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t n) {
+  if (op < 0 || op >= FO_NOPS || (field_words(op, 1) && !b) || !a || !out) return -1;
+  const size_t wa = field_words(op, 0), wb = field_words(op, 1), wo = field_words(op, 2);
+  for (size_t i = 0; i < n; i++) field_op(op, a + i * wa, b + i * wb, out + i * wo, K);
+  return 0;
+}
+extern "C" int emul_field_words(int op, int which) {
+  return (op < 0 || op >= FO_NOPS || which < 0 || which > 2) ? -1 : field_words(op, which);
+}
