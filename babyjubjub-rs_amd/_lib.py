@@ -53,6 +53,10 @@ BASES_SYMBOLS = ("bjj_base_create", "bjj_base_free", "bjj_base_info", "bjj_base_
 BJJ_MAX_BASES = 8
 # ... and include/bjj_hip_signer.h
 SIGNER_SYMBOLS = ("bjj_eddsa_verify_signer", "bjj_eddsa_verify_signer_dev", "bjj_schnorr_verify_signer", "bjj_schnorr_verify_signer_dev")
+# ... and include/bjj_hip_signer_set.h
+SIGNER_SET_SYMBOLS = ("bjj_signer_set_create", "bjj_signer_set_free", "bjj_signer_set_info", "bjj_signer_set_check",
+                      "bjj_eddsa_verify_set", "bjj_eddsa_verify_set_dev", "bjj_schnorr_verify_set", "bjj_schnorr_verify_set_dev")
+BJJ_VERIFY_BAD_SIGNER = 3
 
 
 class BjjInfo(ctypes.Structure):
@@ -198,6 +202,14 @@ def load():
     lib.bjj_eddsa_verify_signer_dev.argtypes = [vp, vp, vp, vp, vp, sz, vp, vp]
     lib.bjj_schnorr_verify_signer.argtypes = [vp, vp, vp, vp, vp, sz, vp]
     lib.bjj_schnorr_verify_signer_dev.argtypes = [vp, vp, vp, vp, vp, sz, vp, vp]
+    lib.bjj_signer_set_create.argtypes = [vp, vp, sz, ci, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_int64)]
+    lib.bjj_signer_set_free.argtypes = [vp, vp]
+    lib.bjj_signer_set_info.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_uint64)]
+    lib.bjj_signer_set_check.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_uint64)]
+    lib.bjj_eddsa_verify_set.argtypes = [vp, vp, vp, vp, vp, vp, sz, vp]
+    lib.bjj_eddsa_verify_set_dev.argtypes = [vp, vp, vp, vp, vp, vp, sz, vp, vp]
+    lib.bjj_schnorr_verify_set.argtypes = [vp, vp, vp, vp, vp, vp, sz, vp]
+    lib.bjj_schnorr_verify_set_dev.argtypes = [vp, vp, vp, vp, vp, vp, sz, vp, vp]
     # multi-GPU
     pd = ctypes.POINTER(ctypes.c_double)
     lib.bjj_multi_init.argtypes = [ctypes.POINTER(ci), ci, ci, ctypes.POINTER(vp)]

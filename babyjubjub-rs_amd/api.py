@@ -28,7 +28,11 @@ SUBORDER = 218882428718392752222464057452572750886145117772685380736017252875875
 
 
 class BjjError(RuntimeError):
-    pass
+    """API misuse or a failed library call; `code` is the library's return code (a BJJ_E_* value) when a call returned one"""
+
+    def __init__(self, msg, code=None):
+        super().__init__(msg)
+        self.code = code
 
 
 def _as_u8(a, width, name):
@@ -79,6 +83,7 @@ class Context:
     def __init__(self, device=0, window_bits=0, _borrowed=None):
         self.lib = _lib.load()
         self._owned = _borrowed is None
+        self._sets = []                                               # SignerSet objects that are still open
         if _borrowed is not None:  # a per-device context owned by a MultiContext
             self.handle = ctypes.c_void_p(_borrowed)
             return
@@ -92,6 +97,8 @@ class Context:
         if getattr(self, "handle", None):
             for b in list(getattr(self, "_bases", [])):               # FixedBase objects that were never closed
                 b.close()
+            for t in list(self._sets):                                # ... and SignerSet objects
+                t.close()
             for ptr in list(getattr(self, "_pinned", {}).values()):   # arrays from host_empty that were never released
                 self.lib.bjj_host_free(self.handle, ptr)
             self._pinned = {}
@@ -107,7 +114,7 @@ class Context:
 
     def _ck(self, rc, what):
         if rc != _lib.BJJ_OK:
-            raise BjjError("%s failed (%d): %s" % (what, rc, self.lib.bjj_last_error().decode()))
+            raise BjjError("%s failed (%d): %s" % (what, rc, self.lib.bjj_last_error().decode()), rc)
 
     def info(self):
         i = _lib.BjjInfo()
@@ -384,6 +391,53 @@ class Context:
         self._ck(self.lib.bjj_schnorr_verify_signer_dev(self.handle, self._signer_handle(base, "schnorr_verify_signer_dev"), d_r, d_s, d_msg,
                                                         n, d_ok, stream), "bjj_schnorr_verify_signer_dev")
 
+    # ---- verification against a set of signers' tables, by per-item index (include/bjj_hip_signer_set.h) ----
+    def signer_set(self, pks, window_bits=0):
+        """the fixed-base tables of k public keys in one device allocation -> SignerSet (bjj_signer_set_create).  pks: k points
+        ((x, y) ints) or k 64-byte records.  window_bits: 0 = 8, or 4..16.  BjjError names the first key that is not on the curve.
+        BjjError.code is the library's return code (BJJ_E_NOMEM when the device refuses the allocation).  Freed with close() or with
+        the context."""
+        rec = _as_u8(pks, 64, "pks")
+        k = rec.size // 64
+        h, first = ctypes.c_void_p(), ctypes.c_int64(-1)
+        rc = self.lib.bjj_signer_set_create(self.handle, rec.ctypes.data if k else None, k, int(window_bits), ctypes.byref(h), ctypes.byref(first))
+        if rc != _lib.BJJ_OK and first.value >= 0:
+            raise BjjError("signer_set: key %d is not on the curve" % first.value, rc)
+        self._ck(rc, "bjj_signer_set_create")
+        t = SignerSet(self, h)
+        self._sets.append(t)
+        return t
+
+    def _set_handle(self, sset, what):
+        if not isinstance(sset, SignerSet) or sset.ctx is not self or not sset.handle:
+            raise BjjError("%s: the set is a live SignerSet of this context" % what)
+        return sset.handle.value
+
+    def _verify_set(self, fn, name, sset, idx, r, s, msg):
+        h = self._set_handle(sset, name)
+        a = np.asarray(idx).reshape(-1)
+        if a.dtype.kind not in "ui" or (a.size and (int(a.min()) < 0 or int(a.max()) > 0xFFFFFFFF)):
+            raise BjjError("%s: signer indices are unsigned 32-bit integers" % name)
+        ix = np.ascontiguousarray(a, dtype=np.uint32)
+        rr = _as_u8(r, 64, "r")
+        sv = _as_u8(s, 32, "s")
+        m = _as_u8(msg, 32, "msg")
+        n = sv.size // 32
+        if ix.size != n or rr.size != n * 64 or m.size != n * 32:
+            raise BjjError("%s: array lengths disagree" % name)
+        ok = np.empty(n, dtype=np.uint8)
+        self._ck(fn(self.handle, h, ix.ctypes.data, rr.ctypes.data, sv.ctypes.data, m.ctypes.data, n, ok.ctypes.data), "bjj_" + name)
+        return ok
+
+    def eddsa_verify_set_dev(self, sset, d_idx, d_r, d_s, d_msg, n, d_ok, stream=0):
+        """bjj_eddsa_verify_set_dev: d_idx = n uint32 signer indices; the other arrays as eddsa_verify_signer_dev"""
+        self._ck(self.lib.bjj_eddsa_verify_set_dev(self.handle, self._set_handle(sset, "eddsa_verify_set_dev"), d_idx, d_r, d_s, d_msg, n,
+                                                   d_ok, stream), "bjj_eddsa_verify_set_dev")
+
+    def schnorr_verify_set_dev(self, sset, d_idx, d_r, d_s, d_msg, n, d_ok, stream=0):
+        self._ck(self.lib.bjj_schnorr_verify_set_dev(self.handle, self._set_handle(sset, "schnorr_verify_set_dev"), d_idx, d_r, d_s, d_msg, n,
+                                                     d_ok, stream), "bjj_schnorr_verify_set_dev")
+
     def set_signer_constant_time(self, on=True):
         """signer hardening: public_keys / sign / sign_schnorr scan a small 4-bit table instead of indexing the big one
         with secret digits -- no secret-dependent address or branch; bit-identical results, ~2x slower sign"""
@@ -595,6 +649,48 @@ class FixedBase:
     def verify_schnorr(self, r, s, msg):
         """Schnorr signatures under this point as the public key -> (n,) uint8, 2 = Err (Context.schnorr_verify_signer)"""
         return self.ctx.schnorr_verify_signer(self, r, s, msg)
+
+
+class SignerSet:
+    """The fixed-base tables of a set of public keys (bjj_signer_set, include/bjj_hip_signer_set.h); made by Context.signer_set()."""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self.handle = ctx, handle
+
+    def close(self):
+        """bjj_signer_set_free: waits for the context's enqueued work, then releases the tables"""
+        if getattr(self, "handle", None) and getattr(self.ctx, "handle", None):
+            self.ctx._ck(self.ctx.lib.bjj_signer_set_free(self.ctx.handle, self.handle), "bjj_signer_set_free")
+            self.ctx._sets.remove(self)
+        self.handle = None
+
+    def _live(self, what):
+        if not self.handle:
+            raise BjjError("%s: the signer set is closed" % what)
+
+    def info(self):
+        """-> (n_signers, window_bits, n_windows, table_bytes)"""
+        self._live("info")
+        k, w, nw, tb = ctypes.c_uint64(), ctypes.c_int(), ctypes.c_int(), ctypes.c_uint64()
+        self.ctx._ck(self.ctx.lib.bjj_signer_set_info(self.handle, ctypes.byref(k), ctypes.byref(w), ctypes.byref(nw), ctypes.byref(tb)),
+                     "bjj_signer_set_info")
+        return k.value, w.value, nw.value, tb.value
+
+    def check(self):
+        """number of violated link conditions over the tables of all signers (0 = sound), checked on the device"""
+        self._live("check")
+        bad = ctypes.c_uint64(0)
+        self.ctx._ck(self.ctx.lib.bjj_signer_set_check(self.ctx.handle, self.handle, ctypes.byref(bad)), "bjj_signer_set_check")
+        return bad.value
+
+    def verify(self, idx, r_b8, s, msg):
+        """EdDSA-Poseidon signatures (R, s) over msg, item i under key idx[i] of the set -> (n,) uint8: what eddsa_verify gives with
+        the keys gathered by index, 3 where idx[i] is not an index of the set (bjj_eddsa_verify_set)"""
+        return self.ctx._verify_set(self.ctx.lib.bjj_eddsa_verify_set, "eddsa_verify_set", self, idx, r_b8, s, msg)
+
+    def verify_schnorr(self, idx, r, s, msg):
+        """Schnorr signatures, item i under key idx[i] -> (n,) uint8: 1 / 0, 2 = Err (msg > Q), 3 = no such signer"""
+        return self.ctx._verify_set(self.ctx.lib.bjj_schnorr_verify_set, "schnorr_verify_set", self, idx, r, s, msg)
 
 
 class MultiContext:

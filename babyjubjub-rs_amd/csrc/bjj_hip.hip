@@ -39,9 +39,11 @@
 #include "../../include/bjj_hip_msm_batch.h"
 #include "../../include/bjj_hip_bases.h"
 #include "../../include/bjj_hip_signer.h"
+#include "../../include/bjj_hip_signer_set.h"
 #include "bjj_device.hpp"
 #include "bases.hpp"
 #include "signer.hpp"
+#include "signer_set.hpp"
 #include "bjj_launch.hpp"
 #include "msm.hpp"
 #include "copy_pool.hpp"
@@ -187,6 +189,16 @@ struct bjj_base {
   DevBlock<u32> table;       // [window][digit 0 .. 2^(W-1)] x 128 B
   DevBlock<u32> bases;       // P_j = 2^(W j) * P, one Niels entry per window
 };
+// The tables of a set of k signers (include/bjj_hip_signer_set.h): ONE allocation, signer j at entry offset j * nwin * (2^(W-1) + 1)
+// (signer_set.hpp).  Owned by its context (bjj_ctx::user_sets); a handle that exists is a set whose k tables passed their check.
+struct bjj_signer_set {
+  bjj_ctx* ctx = nullptr;
+  int W = 0, nwin = 0;
+  size_t k = 0;
+  DevBlock<u32> table;       // [signer][window][digit 0 .. 2^(W-1)] x 128 B
+  DevBlock<u32> bases;       // P_{s,j} = 2^(W j) * key_s, one Niels entry per signer and window
+  DevBlock<u32> keys;        // the k keys as the hash takes them: SET_KEY_WORDS words each
+};
 struct bjj_ctx {
   int device = 0;
   int cus = 0;
@@ -200,6 +212,8 @@ struct bjj_ctx {
   int lanes_bases = 512;         // resident lanes per CU of bjj_k_mul_bases
   int lanes_signer = 512;        // resident lanes per CU of the bjj_k_*_verify_signer kernels
   std::vector<bjj_base*> user_bases;   // the tables bjj_base_create made and bjj_base_free has not released yet
+  int lanes_set = 512;           // resident lanes per CU of the bjj_k_*_verify_set kernels
+  std::vector<bjj_signer_set*> user_sets;   // the sets bjj_signer_set_create made and bjj_signer_set_free has not released yet
   int verify_mode = -1;          // -1 = per call (persistent waves for one launch > 2^21 items that runs alone, groups otherwise), 0 / 1 = forced (BJJ_VERIFY_DISPATCH)
   int k2_variant = -1;           // -1 = per call (tiles for a launch that runs alone, grid-strided while another is in flight), 0 / 1 = forced (BJJ_K2_VARIANT)
   int k1_variant = -1;           // -1 = per call (two-workgroup shape while another launch of the context is in flight), 0 / 1 = forced (BJJ_K1_VARIANT)
@@ -497,6 +511,8 @@ static void ctx_destroy(bjj_ctx* c) {
   for (StreamMark& k : c->marks) if (k.ev) hipEventDestroy(k.ev);
   for (bjj_base* b : c->user_bases) delete b;   // tables the caller never freed
   c->user_bases.clear();
+  for (bjj_signer_set* t : c->user_sets) delete t;   // ... and the signer sets
+  c->user_sets.clear();
   delete c->pool;   // joins the copy workers
   c->pool = nullptr;
   for (hipEvent_t e : c->ev_in) hipEventDestroy(e);
@@ -556,6 +572,7 @@ int bjj_init(int device, int window_bits, bjj_ctx** out_ctx) {
   c->lanes_fixed_2x256 = bjjk::fixed_base_lanes_per_cu(1);
   c->lanes_bases = bjjk::bases_lanes_per_cu();
   c->lanes_signer = bjjk::signer_lanes_per_cu();
+  c->lanes_set = bjjk::set_lanes_per_cu();
   if (const char* e = getenv("BJJ_VERIFY_DISPATCH")) {
     if (e[0] == '0' || e[0] == '1') c->verify_mode = e[0] - '0';
   }
@@ -1927,6 +1944,168 @@ int bjj_schnorr_verify_signer(bjj_ctx* c, const bjj_base* signer, const uint8_t*
 int bjj_schnorr_verify_signer_dev(bjj_ctx* c, const bjj_base* signer, const void* d_r_xy, const void* d_s, const void* d_msg, size_t n, void* d_ok,
                                   void* stream) {
   return verify_signer_dev(c, true, signer, d_r_xy, d_s, d_msg, n, d_ok, stream, "bjj_schnorr_verify_signer_dev");
+}
+
+// ---- verification against a set of signers' tables, by per-item index (include/bjj_hip_signer_set.h) ------------------------------
+#define BJJ_SET_DEFAULT_WINDOW_BITS 8
+#define BJJ_SET_MAX_WINDOW_BITS 16
+static_assert(BJJ_VERIFY_BAD_SIGNER == BJJ_SET_BAD_SIGNER, "include/bjj_hip_signer_set.h and signer_set.hpp disagree");
+static bool set_of_ctx(const bjj_ctx* c, const bjj_signer_set* t) {
+  for (const bjj_signer_set* k : c->user_sets) if (k == t) return true;
+  return false;
+}
+static int set_run_check(bjj_ctx* c, const bjj_signer_set* t, unsigned long long* bad, const char* who) {
+  DevBlock<unsigned long long> d_bad;
+  hipError_t e = d_bad.grow(sizeof(unsigned long long), NO_WAIT);
+  if (e == hipSuccess) e = hipMemsetAsync(d_bad, 0, sizeof(unsigned long long), c->stream);
+  if (e == hipSuccess) e = bjjk::check_signer_set(c->stream, c->cus * 8, t->table, t->bases, t->keys, t->k, t->W, t->nwin, d_bad);
+  if (e == hipSuccess) e = hipMemcpyAsync(bad, d_bad, sizeof(*bad), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) return set_err(BJJ_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
+  return BJJ_OK;
+}
+int bjj_signer_set_create(bjj_ctx* c, const uint8_t* pks_xy, size_t k, int window_bits, bjj_signer_set** out, int64_t* out_first_off_curve) {
+  CHECK_CTX(c, "bjj_signer_set_create");
+  if (!pks_xy || !out) return set_err(BJJ_E_INVALID, "bjj_signer_set_create: NULL argument");
+  if (window_bits != 0 && (window_bits < 4 || window_bits > BJJ_SET_MAX_WINDOW_BITS))
+    return set_err(BJJ_E_INVALID, "bjj_signer_set_create: window_bits must be 0 (default, 8) or 4..16");
+  const int W = window_bits ? window_bits : BJJ_SET_DEFAULT_WINDOW_BITS;
+  // the gather carries slot numbers as 32-bit words: before any point is looked at, before anything is allocated
+  if (!set_slots_fit((u64)k, W))
+    return set_err(BJJ_E_INVALID, "bjj_signer_set_create: k must be 1 .. 2^32 / (n_windows * (2^(window_bits-1) + 1)) = " +
+                                      std::to_string((((u64)1) << 32) / set_entries_per_signer(W)));
+  std::vector<u32> keys;
+  try { keys.resize(k * SET_KEY_WORDS); } catch (...) { return set_err(BJJ_E_NOMEM, "bjj_signer_set_create: out of host memory"); }
+  for (size_t j = 0; j < k; j++) {
+    u32 xy[16];
+    memcpy(xy, pks_xy + j * 64, 64);
+    if (!point_words_on_curve(xy)) {
+      if (out_first_off_curve) *out_first_off_curve = (int64_t)j;
+      return set_err(BJJ_E_INVALID, "bjj_signer_set_create: key " + std::to_string(j) + " is not on the curve");
+    }
+    set_key_store(keys.data() + j * SET_KEY_WORDS, signer_point(xy));
+  }
+  ENTER_DEVICE(c->device);
+  bjj_signer_set* t = new (std::nothrow) bjj_signer_set();
+  if (!t) return set_err(BJJ_E_NOMEM, "bjj_signer_set_create: out of host memory");
+  t->ctx = c; t->W = W; t->nwin = base_nwin(W); t->k = k;
+  const size_t bytes = k * (size_t)set_entries_per_signer(W) * NIELS_WORDS * sizeof(u32);
+  hipError_t e = t->table.grow(bytes, NO_WAIT);
+  if (e == hipSuccess) e = t->bases.grow(k * (size_t)t->nwin * NIELS_WORDS * sizeof(u32), NO_WAIT);
+  if (e == hipSuccess) e = t->keys.grow(keys.size() * sizeof(u32), NO_WAIT);
+  if (e != hipSuccess) {
+    (void)hipGetLastError(); delete t;
+    return set_err(BJJ_E_NOMEM, "bjj_signer_set_create: cannot allocate the tables (" + std::to_string(bytes >> 20) + " MB)");
+  }
+  e = hipMemcpyAsync(t->keys, keys.data(), keys.size() * sizeof(u32), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = bjjk::build_signer_set(c->stream, t->table, t->bases, t->keys, k, W, t->nwin);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // `keys` is this call's own memory
+  if (e != hipSuccess) { delete t; return set_err(BJJ_E_HIP, std::string("bjj_signer_set_create: table build failed: ") + hipGetErrorString(e)); }
+  unsigned long long bad = 1;   // a handle that exists is a set that passed (the rule of bjj_base_create)
+  { int rc = set_run_check(c, t, &bad, "bjj_signer_set_create"); if (rc) { delete t; return rc; } }
+  if (bad != 0) { delete t; return set_err(BJJ_E_HIP, "bjj_signer_set_create: the tables failed their self-check (" + std::to_string(bad) + " conditions)"); }
+  try { c->user_sets.push_back(t); } catch (...) { delete t; return set_err(BJJ_E_NOMEM, "bjj_signer_set_create: out of host memory"); }
+  if (out_first_off_curve) *out_first_off_curve = -1;
+  *out = t;
+  return BJJ_OK;
+}
+int bjj_signer_set_free(bjj_ctx* c, bjj_signer_set* t) {
+  CHECK_CTX(c, "bjj_signer_set_free");
+  if (!t) return BJJ_OK;
+  if (!set_of_ctx(c, t)) return set_err(BJJ_E_INVALID, "bjj_signer_set_free: not a signer set of this context");
+  ENTER_DEVICE(c->device);
+  { int rc = ctx_wait_enqueued(c); if (rc) return rc; }   // launches that gather from the tables
+  for (size_t i = 0; i < c->user_sets.size(); i++)
+    if (c->user_sets[i] == t) { c->user_sets.erase(c->user_sets.begin() + (long)i); break; }
+  delete t;
+  return BJJ_OK;
+}
+int bjj_signer_set_info(const bjj_signer_set* t, uint64_t* n_signers, int* window_bits, int* n_windows, uint64_t* table_bytes) {
+  if (!t) return set_err(BJJ_E_INVALID, "bjj_signer_set_info: set is NULL");
+  if (n_signers) *n_signers = (uint64_t)t->k;
+  if (window_bits) *window_bits = t->W;
+  if (n_windows) *n_windows = t->nwin;
+  if (table_bytes) *table_bytes = (uint64_t)t->table.bytes;
+  return BJJ_OK;
+}
+int bjj_signer_set_check(bjj_ctx* c, const bjj_signer_set* t, uint64_t* n_bad) {
+  CHECK_CTX(c, "bjj_signer_set_check");
+  if (!t || !n_bad) return set_err(BJJ_E_INVALID, "bjj_signer_set_check: NULL argument");
+  if (!set_of_ctx(c, t)) return set_err(BJJ_E_INVALID, "bjj_signer_set_check: not a signer set of this context");
+  ENTER_DEVICE(c->device);
+  unsigned long long bad = 0;
+  { int rc = set_run_check(c, t, &bad, "bjj_signer_set_check"); if (rc) return rc; }
+  *n_bad = (uint64_t)bad;
+  return BJJ_OK;
+}
+// argument checks of both forms; fills the descriptors (the set's tables: mod 8l; the context's B8 table: mod l)
+static int verify_set_check(bjj_ctx* c, const bjj_signer_set* t, size_t n, const char* who, SetArgs* A) {
+  if (!c) return set_err(BJJ_E_INVALID, std::string(who) + ": ctx is NULL");
+  if (!t) return set_err(BJJ_E_INVALID, std::string(who) + ": set is NULL");
+  if (!set_of_ctx(c, t)) return set_err(BJJ_E_INVALID, std::string(who) + ": set is not a signer set of this context");
+  CHECK_N(n);
+  memset(A, 0, sizeof(*A));
+  A->T.table = t->table.p; A->T.W = t->W; A->T.nwin = t->nwin; A->T.mod_l = 0;
+  A->L.table = c->table.p; A->L.W = c->W; A->L.nwin = c->nwin; A->L.mod_l = 1;
+  A->keys = t->keys.p; A->k = (u32)t->k; A->eps = (u32)set_entries_per_signer(t->W);
+  return BJJ_OK;
+}
+// No scratch set: the kernel keeps everything in registers and LDS, so calls on different streams share nothing.
+static int verify_set_dev(bjj_ctx* c, bool schnorr, const bjj_signer_set* t, const void* d_idx, const void* d_r, const void* d_s,
+                          const void* d_msg, size_t n, void* d_ok, void* stream, const char* who) {
+  SetArgs A;
+  { int rc = verify_set_check(c, t, n, who, &A); if (rc) return rc; }
+  if (n == 0) return BJJ_OK;
+  if (!d_idx || !d_r || !d_s || !d_msg || !aligned16(d_idx) || !aligned16(d_r) || !aligned16(d_s) || !aligned16(d_msg))
+    return set_err(BJJ_E_INVALID, std::string(who) + ": NULL or not 16-byte aligned device pointer");
+  if (!d_ok) return set_err(BJJ_E_INVALID, std::string(who) + ": d_ok is NULL");
+  DEV_ENTER(c, stream);
+  LAUNCHCK_S(bjjk::verify_set(st, c->cus, c->lanes_set, schnorr, A, (const uint32_t*)d_idx, (const uint8_t*)d_r, (const uint8_t*)d_s,
+                              (const uint8_t*)d_msg, n, (uint8_t*)d_ok), who);
+  DEV_LEAVE(c);
+}
+// Synchronous: the four arrays go to the set's block with one copy each (pinned or pageable), one launch, one copy out.
+static int verify_set_host(bjj_ctx* c, bool schnorr, const bjj_signer_set* t, const uint32_t* idx, const uint8_t* r, const uint8_t* s,
+                           const uint8_t* msg, size_t n, uint8_t* ok, const char* who) {
+  SetArgs A;
+  { int rc = verify_set_check(c, t, n, who, &A); if (rc) return rc; }
+  if (n == 0) return BJJ_OK;
+  if (!idx || !r || !s || !msg || !ok) return set_err(BJJ_E_INVALID, std::string(who) + ": NULL buffer");
+  hipStream_t st = c->stream;
+  ENTER_DEVICE(c->device);
+  ScratchSet* S = pick_set(c, st);
+  const size_t o_s = up256(n * 64), o_msg = o_s + up256(n * 32), o_idx = o_msg + up256(n * 32), o_ok = o_idx + up256(n * 4);
+  if (S->bases_io.grow(o_ok + n) != hipSuccess) {
+    (void)hipGetLastError();
+    return set_err(BJJ_E_NOMEM, std::string(who) + ": cannot allocate " + std::to_string((o_ok + n) >> 20) + " MB of device staging");
+  }
+  { int rc = set_enter(c, S, st); if (rc) return rc; }
+  uint8_t* blk = S->bases_io;
+  HIPCK(hipMemcpyAsync(blk, r, n * 64, hipMemcpyHostToDevice, st));
+  HIPCK(hipMemcpyAsync(blk + o_s, s, n * 32, hipMemcpyHostToDevice, st));
+  HIPCK(hipMemcpyAsync(blk + o_msg, msg, n * 32, hipMemcpyHostToDevice, st));
+  HIPCK(hipMemcpyAsync(blk + o_idx, idx, n * 4, hipMemcpyHostToDevice, st));
+  LAUNCHCK_S(bjjk::verify_set(st, c->cus, c->lanes_set, schnorr, A, (const uint32_t*)(blk + o_idx), blk, blk + o_s, blk + o_msg, n, blk + o_ok), who);
+  HIPCK(hipMemcpyAsync(ok, blk + o_ok, n, hipMemcpyDeviceToHost, st));
+  { int rc = set_leave(c, S, st); if (rc) return rc; }
+  HIPCK(hipStreamSynchronize(st));
+  return BJJ_OK;
+}
+int bjj_eddsa_verify_set(bjj_ctx* c, const bjj_signer_set* set, const uint32_t* signer_idx, const uint8_t* r_xy, const uint8_t* s,
+                         const uint8_t* msg, size_t n, uint8_t* ok) {
+  return verify_set_host(c, false, set, signer_idx, r_xy, s, msg, n, ok, "bjj_eddsa_verify_set");
+}
+int bjj_eddsa_verify_set_dev(bjj_ctx* c, const bjj_signer_set* set, const void* d_signer_idx, const void* d_r_xy, const void* d_s,
+                             const void* d_msg, size_t n, void* d_ok, void* stream) {
+  return verify_set_dev(c, false, set, d_signer_idx, d_r_xy, d_s, d_msg, n, d_ok, stream, "bjj_eddsa_verify_set_dev");
+}
+int bjj_schnorr_verify_set(bjj_ctx* c, const bjj_signer_set* set, const uint32_t* signer_idx, const uint8_t* r_xy, const uint8_t* s,
+                           const uint8_t* msg, size_t n, uint8_t* ok) {
+  return verify_set_host(c, true, set, signer_idx, r_xy, s, msg, n, ok, "bjj_schnorr_verify_set");
+}
+int bjj_schnorr_verify_set_dev(bjj_ctx* c, const bjj_signer_set* set, const void* d_signer_idx, const void* d_r_xy, const void* d_s,
+                               const void* d_msg, size_t n, void* d_ok, void* stream) {
+  return verify_set_dev(c, true, set, d_signer_idx, d_r_xy, d_s, d_msg, n, d_ok, stream, "bjj_schnorr_verify_set_dev");
 }
 
 #pragma GCC visibility pop

@@ -19,6 +19,7 @@
 
 namespace bjj { struct BasesArgs; }   // bases.hpp: the per-base descriptors of bjj_k_mul_bases
 namespace bjj { struct SignerArgs; }  // signer.hpp: the two tables and the point of bjj_k_verify_signer
+namespace bjj { struct SetArgs; }     // signer_set.hpp: the set's tables and keys, the B8 table (bjj_k_verify_set)
 
 namespace bjjk {
 
@@ -142,5 +143,16 @@ hipError_t mul_bases(hipStream_t st, int cus, int lanes_per_cu, const bjj::Bases
 int signer_lanes_per_cu();
 hipError_t verify_signer(hipStream_t st, int cus, int lanes_per_cu, bool schnorr, const bjj::SignerArgs& A, const uint8_t* r, const uint8_t* s,
                          const uint8_t* msg, size_t n, uint8_t* ok);
+
+// k_signer_set.hip: the tables of a set of k signers in ONE allocation (signer j at entry offset j * nwin * (2^(W-1) + 1); keys: k
+// records of SET_KEY_WORDS words, bases: k * nwin Niels entries) -- three launches whatever k: window bases and fill
+// (build_signer_set), check (check_signer_set) -- and verify /
+// verify_schnorr against pks[idx[i]] (the shape of verify_signer; ok[i] = 3 for idx[i] >= k)
+int set_lanes_per_cu();
+hipError_t build_signer_set(hipStream_t st, uint32_t* table, uint32_t* bases, const uint32_t* keys, size_t k, int W, int nwin);
+hipError_t check_signer_set(hipStream_t st, int grid, const uint32_t* table, const uint32_t* bases, const uint32_t* keys, size_t k, int W,
+                            int nwin, unsigned long long* d_bad);
+hipError_t verify_set(hipStream_t st, int cus, int lanes_per_cu, bool schnorr, const bjj::SetArgs& A, const uint32_t* idx, const uint8_t* r,
+                      const uint8_t* s, const uint8_t* msg, size_t n, uint8_t* ok);
 
 }  // namespace bjjk
