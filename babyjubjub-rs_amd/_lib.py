@@ -57,6 +57,11 @@ SIGNER_SYMBOLS = ("bjj_eddsa_verify_signer", "bjj_eddsa_verify_signer_dev", "bjj
 SIGNER_SET_SYMBOLS = ("bjj_signer_set_create", "bjj_signer_set_free", "bjj_signer_set_info", "bjj_signer_set_check",
                       "bjj_eddsa_verify_set", "bjj_eddsa_verify_set_dev", "bjj_schnorr_verify_set", "bjj_schnorr_verify_set_dev")
 BJJ_VERIFY_BAD_SIGNER = 3
+# ... and include/bjj_hip_dlog.h
+DLOG_SYMBOLS = ("bjj_dlog_table_create", "bjj_dlog_table_free", "bjj_dlog_table_info", "bjj_dlog_table_check", "bjj_dlog_table_base",
+                "bjj_dlog_max_range_bits", "bjj_dlog", "bjj_dlog_dev")
+BJJ_DLOG_NOT_IN_RANGE, BJJ_DLOG_FOUND, BJJ_DLOG_OFF_CURVE = 0, 1, 2
+BJJ_DLOG_MAX_GIANT_BITS = 16
 
 
 class BjjInfo(ctypes.Structure):
@@ -210,6 +215,14 @@ def load():
     lib.bjj_eddsa_verify_set_dev.argtypes = [vp, vp, vp, vp, vp, vp, sz, vp, vp]
     lib.bjj_schnorr_verify_set.argtypes = [vp, vp, vp, vp, vp, vp, sz, vp]
     lib.bjj_schnorr_verify_set_dev.argtypes = [vp, vp, vp, vp, vp, vp, sz, vp, vp]
+    lib.bjj_dlog_table_create.argtypes = [vp, vp, ci, ctypes.POINTER(vp)]
+    lib.bjj_dlog_table_free.argtypes = [vp, vp]
+    lib.bjj_dlog_table_info.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
+    lib.bjj_dlog_table_check.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_uint64)]
+    lib.bjj_dlog_table_base.argtypes = [vp, vp]
+    lib.bjj_dlog_max_range_bits.argtypes = [vp]
+    lib.bjj_dlog.argtypes = [vp, vp, vp, sz, ci, vp, vp]
+    lib.bjj_dlog_dev.argtypes = [vp, vp, vp, sz, ci, vp, vp, vp]
     # multi-GPU
     pd = ctypes.POINTER(ctypes.c_double)
     lib.bjj_multi_init.argtypes = [ctypes.POINTER(ci), ci, ci, ctypes.POINTER(vp)]

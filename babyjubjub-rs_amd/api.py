@@ -67,6 +67,22 @@ def _as_u8(a, width, name):
     return np.frombuffer(bytes(out), dtype=np.uint8).copy()
 
 
+def _negate_x(points):
+    """(n, 64) canonical affine points (x, y < Q, as the library writes them) -> (-x mod Q, y): Q - x over eight 32-bit limbs with a
+    borrow, vectorised; x = 0 stays 0"""
+    p = np.ascontiguousarray(points, dtype=np.uint8).reshape(-1, 64).copy()
+    x = p[:, :32].copy().view("<u4").astype(np.int64)                      # (n, 8) limbs, little-endian
+    out = np.empty_like(x)
+    borrow = np.zeros(x.shape[0], dtype=np.int64)
+    for i in range(8):
+        d = ((Q >> (32 * i)) & 0xFFFFFFFF) - x[:, i] - borrow
+        borrow = (d < 0).astype(np.int64)
+        out[:, i] = d + (borrow << 32)
+    out[~x.any(axis=1)] = 0
+    p[:, :32] = out.astype("<u4").view(np.uint8)
+    return p
+
+
 def _ints(arr, per_item):
     b = arr.tobytes()
     vals = [int.from_bytes(b[i:i + 32], "little") for i in range(0, len(b), 32)]
@@ -84,6 +100,7 @@ class Context:
         self.lib = _lib.load()
         self._owned = _borrowed is None
         self._sets = []                                               # SignerSet objects that are still open
+        self._dlogs = []                                              # DlogTable objects that are still open
         if _borrowed is not None:  # a per-device context owned by a MultiContext
             self.handle = ctypes.c_void_p(_borrowed)
             return
@@ -98,6 +115,8 @@ class Context:
             for b in list(getattr(self, "_bases", [])):               # FixedBase objects that were never closed
                 b.close()
             for t in list(self._sets):                                # ... and SignerSet objects
+                t.close()
+            for t in list(self._dlogs):                               # ... and DlogTable objects
                 t.close()
             for ptr in list(getattr(self, "_pinned", {}).values()):   # arrays from host_empty that were never released
                 self.lib.bjj_host_free(self.handle, ptr)
@@ -438,6 +457,56 @@ class Context:
         self._ck(self.lib.bjj_schnorr_verify_set_dev(self.handle, self._set_handle(sset, "schnorr_verify_set_dev"), d_idx, d_r, d_s, d_msg, n,
                                                      d_ok, stream), "bjj_schnorr_verify_set_dev")
 
+    # ---- small-range discrete logarithms (include/bjj_hip_dlog.h) ----
+    def dlog_table(self, point=None, baby_bits=0):
+        """the baby-step table of a base point G -> DlogTable (bjj_dlog_table_create).  point: (x, y) ints or a 64-byte record,
+        None = B8.  baby_bits: 0 = 24 (512 MiB), or 4..28.  BjjError (code BJJ_E_INVALID) for a point off the curve or of order <= 8.  Freed
+        with close() or with the context."""
+        rec = None if point is None else _as_u8([point] if isinstance(point, tuple) else point, 64, "point")
+        if rec is not None and rec.size != 64:
+            raise BjjError("dlog_table: one point")
+        h = ctypes.c_void_p()
+        self._ck(self.lib.bjj_dlog_table_create(self.handle, None if rec is None else rec.ctypes.data, int(baby_bits), ctypes.byref(h)),
+                 "bjj_dlog_table_create")
+        t = DlogTable(self, h)
+        self._dlogs.append(t)
+        return t
+
+    def _dlog_handle(self, table, what):
+        if not isinstance(table, DlogTable) or table.ctx is not self or not table.handle:
+            raise BjjError("%s: the table is a live DlogTable of this context" % what)
+        return table.handle.value
+
+    def dlog(self, table, points, range_bits):
+        """m with m * G = points[i], 0 <= m < 2^range_bits -> (m: (n,) uint64, ok: (n,) uint8): ok 1 = found, 0 = not in range
+        (m = 2^64 - 1), 2 = the point is not on the curve (bjj_dlog)"""
+        h = self._dlog_handle(table, "dlog")
+        p = _as_u8(points, 64, "points")
+        n = p.size // 64
+        m = np.empty(n, dtype=np.uint64)
+        ok = np.empty(n, dtype=np.uint8)
+        self._ck(self.lib.bjj_dlog(self.handle, h, p.ctypes.data, n, int(range_bits), m.ctypes.data, ok.ctypes.data), "bjj_dlog")
+        return m, ok
+
+    def dlog_dev(self, table, d_pts, n, range_bits, d_out_m, d_ok, stream=0):
+        """bjj_dlog_dev: d_pts = n 64-byte records, d_out_m = n uint64, d_ok = n bytes, all on the device"""
+        self._ck(self.lib.bjj_dlog_dev(self.handle, self._dlog_handle(table, "dlog_dev"), d_pts, n, int(range_bits), d_out_m, d_ok, stream),
+                 "bjj_dlog_dev")
+
+    def elgamal_decrypt(self, table, sk, c1, c2, range_bits):
+        """exponential ElGamal: m from (C1, C2) = (r * G, m * G + r * PK) with PK = sk * G and `table` the DlogTable of G ->
+        (m, ok) as dlog().  M = C2 - sk * C1 by mul_var_base and point_add (-(x, y) = (-x, y), negated on the host), then the
+        logarithm of M.  A wrong key gives ok = 0, not a wrong m."""
+        a = _as_u8(c1, 64, "c1")
+        b = _as_u8(c2, 64, "c2")
+        n = a.size // 64
+        if b.size != a.size:
+            raise BjjError("elgamal_decrypt: array lengths disagree")
+        if n == 0:
+            return np.empty(0, dtype=np.uint64), np.empty(0, dtype=np.uint8)
+        t = self.mul_var_base(a, np.tile(_as_u8([int(sk)], 32, "sk"), n))
+        return self.dlog(table, self.point_add(b, _negate_x(t)), range_bits)
+
     def set_signer_constant_time(self, on=True):
         """signer hardening: public_keys / sign / sign_schnorr scan a small 4-bit table instead of indexing the big one
         with secret digits -- no secret-dependent address or branch; bit-identical results, ~2x slower sign"""
@@ -691,6 +760,53 @@ class SignerSet:
     def verify_schnorr(self, idx, r, s, msg):
         """Schnorr signatures, item i under key idx[i] -> (n,) uint8: 1 / 0, 2 = Err (msg > Q), 3 = no such signer"""
         return self.ctx._verify_set(self.ctx.lib.bjj_schnorr_verify_set, "schnorr_verify_set", self, idx, r, s, msg)
+
+
+class DlogTable:
+    """The baby-step table of one base point (bjj_dlog_table, include/bjj_hip_dlog.h); made by Context.dlog_table()."""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self.handle = ctx, handle
+
+    def close(self):
+        """bjj_dlog_table_free: waits for the context's enqueued work, then releases the table"""
+        if getattr(self, "handle", None) and getattr(self.ctx, "handle", None):
+            self.ctx._ck(self.ctx.lib.bjj_dlog_table_free(self.ctx.handle, self.handle), "bjj_dlog_table_free")
+            self.ctx._dlogs.remove(self)
+        self.handle = None
+
+    def _live(self, what):
+        if not self.handle:
+            raise BjjError("%s: the table is closed" % what)
+
+    def info(self):
+        """-> (baby_bits, entries, table_bytes)"""
+        self._live("info")
+        b, e, tb = ctypes.c_int(), ctypes.c_uint64(), ctypes.c_uint64()
+        self.ctx._ck(self.ctx.lib.bjj_dlog_table_info(self.handle, ctypes.byref(b), ctypes.byref(e), ctypes.byref(tb)), "bjj_dlog_table_info")
+        return b.value, e.value, tb.value
+
+    def base(self):
+        """the base point as (x, y), coordinates reduced"""
+        self._live("base")
+        out = np.empty(64, dtype=np.uint8)
+        self.ctx._ck(self.ctx.lib.bjj_dlog_table_base(self.handle, out.ctypes.data), "bjj_dlog_table_base")
+        return _ints(out, 2)[0]
+
+    def max_range_bits(self):
+        self._live("max_range_bits")
+        return self.ctx.lib.bjj_dlog_max_range_bits(self.handle)
+
+    def check(self):
+        """number of violated conditions of the table's self-check (0 = sound), checked on the device"""
+        self._live("check")
+        bad = ctypes.c_uint64(0)
+        self.ctx._ck(self.ctx.lib.bjj_dlog_table_check(self.ctx.handle, self.handle, ctypes.byref(bad)), "bjj_dlog_table_check")
+        return bad.value
+
+    def dlog(self, points, range_bits):
+        """-> (m: (n,) uint64, ok: (n,) uint8), see Context.dlog"""
+        return self.ctx.dlog(self, points, range_bits)
 
 
 class MultiContext:

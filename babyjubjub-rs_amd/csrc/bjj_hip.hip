@@ -40,10 +40,12 @@
 #include "../../include/bjj_hip_bases.h"
 #include "../../include/bjj_hip_signer.h"
 #include "../../include/bjj_hip_signer_set.h"
+#include "../../include/bjj_hip_dlog.h"
 #include "bjj_device.hpp"
 #include "bases.hpp"
 #include "signer.hpp"
 #include "signer_set.hpp"
+#include "dlog.hpp"
 #include "bjj_launch.hpp"
 #include "msm.hpp"
 #include "copy_pool.hpp"
@@ -199,6 +201,32 @@ struct bjj_signer_set {
   DevBlock<u32> bases;       // P_{s,j} = 2^(W j) * key_s, one Niels entry per signer and window
   DevBlock<u32> keys;        // the k keys as the hash takes them: SET_KEY_WORDS words each
 };
+// The baby-step table of one base point (include/bjj_hip_dlog.h, dlog.hpp).  Owned by its context (bjj_ctx::user_dlogs); a handle
+// that exists is a table that passed its check.
+struct bjj_dlog_table {
+  bjj_ctx* ctx = nullptr;
+  int b = 0;                               // baby_bits
+  uint8_t base_xy[64] = {0};               // the base point, coordinates reduced mod r
+  DevBlock<unsigned long long> slots;      // 2^(b+2) slots {tag, j + 1}
+  DevBlock<u32> params;                    // DLOG_PARAM_WORDS words: Niels(G), Niels(-2^b G), Niels(-2^(b+1) G), the base's record
+};
+// Giant steps ONE launch of bjj_dlog / bjj_dlog_dev performs at most, summed over its items; a longer call is cut into consecutive
+// launches: 2^27 steps fill the chip for 29 ms.  BJJ_DLOG_LAUNCH_STEPS, read once here, lowers or raises it
+// (tests force the cut with it).  Beside it, no launch walks an item further than BJJ_DLOG_LAUNCH_STEPS_PER_ITEM steps -- a workgroup
+// takes 56 us per step whatever the rest of the chip does, so 512 steps are 29 ms for a launch of few items too -- nor, where the
+// bound would allow fewer, less than BJJ_DLOG_LAUNCH_STEPS_MIN (a later launch pays a ladder worth 13 steps to get to its first).
+#define BJJ_DLOG_LAUNCH_STEPS_DEFAULT ((uint64_t)1 << 27)
+#define BJJ_DLOG_LAUNCH_STEPS_MIN 64
+#define BJJ_DLOG_LAUNCH_STEPS_PER_ITEM 512
+static uint64_t dlog_launch_steps_from_env() {
+  uint64_t v = BJJ_DLOG_LAUNCH_STEPS_DEFAULT;
+  if (const char* e = getenv("BJJ_DLOG_LAUNCH_STEPS")) {
+    char* end = nullptr;
+    const unsigned long long x = strtoull(e, &end, 10);
+    if (end != e && *end == 0 && x >= BJJ_DLOG_LAUNCH_STEPS_MIN) v = (uint64_t)x;
+  }
+  return v;
+}
 struct bjj_ctx {
   int device = 0;
   int cus = 0;
@@ -214,6 +242,8 @@ struct bjj_ctx {
   std::vector<bjj_base*> user_bases;   // the tables bjj_base_create made and bjj_base_free has not released yet
   int lanes_set = 512;           // resident lanes per CU of the bjj_k_*_verify_set kernels
   std::vector<bjj_signer_set*> user_sets;   // the sets bjj_signer_set_create made and bjj_signer_set_free has not released yet
+  std::vector<bjj_dlog_table*> user_dlogs;  // the tables bjj_dlog_table_create made and bjj_dlog_table_free has not released yet
+  uint64_t dlog_launch_steps = 0;           // giant steps one launch of bjj_dlog performs at most, over all its items (BJJ_DLOG_LAUNCH_STEPS)
   int verify_mode = -1;          // -1 = per call (persistent waves for one launch > 2^21 items that runs alone, groups otherwise), 0 / 1 = forced (BJJ_VERIFY_DISPATCH)
   int k2_variant = -1;           // -1 = per call (tiles for a launch that runs alone, grid-strided while another is in flight), 0 / 1 = forced (BJJ_K2_VARIANT)
   int k1_variant = -1;           // -1 = per call (two-workgroup shape while another launch of the context is in flight), 0 / 1 = forced (BJJ_K1_VARIANT)
@@ -513,6 +543,8 @@ static void ctx_destroy(bjj_ctx* c) {
   c->user_bases.clear();
   for (bjj_signer_set* t : c->user_sets) delete t;   // ... and the signer sets
   c->user_sets.clear();
+  for (bjj_dlog_table* t : c->user_dlogs) delete t;   // ... and the discrete-logarithm tables
+  c->user_dlogs.clear();
   delete c->pool;   // joins the copy workers
   c->pool = nullptr;
   for (hipEvent_t e : c->ev_in) hipEventDestroy(e);
@@ -573,6 +605,7 @@ int bjj_init(int device, int window_bits, bjj_ctx** out_ctx) {
   c->lanes_bases = bjjk::bases_lanes_per_cu();
   c->lanes_signer = bjjk::signer_lanes_per_cu();
   c->lanes_set = bjjk::set_lanes_per_cu();
+  c->dlog_launch_steps = dlog_launch_steps_from_env();
   if (const char* e = getenv("BJJ_VERIFY_DISPATCH")) {
     if (e[0] == '0' || e[0] == '1') c->verify_mode = e[0] - '0';
   }
@@ -2107,6 +2140,8 @@ int bjj_schnorr_verify_set_dev(bjj_ctx* c, const bjj_signer_set* set, const void
                                const void* d_msg, size_t n, void* d_ok, void* stream) {
   return verify_set_dev(c, true, set, d_signer_idx, d_r_xy, d_s, d_msg, n, d_ok, stream, "bjj_schnorr_verify_set_dev");
 }
+
+#include "bjj_dlog.inc"
 
 #pragma GCC visibility pop
 }  // extern "C"

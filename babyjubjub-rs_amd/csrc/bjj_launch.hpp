@@ -155,4 +155,14 @@ hipError_t check_signer_set(hipStream_t st, int grid, const uint32_t* table, con
 hipError_t verify_set(hipStream_t st, int cus, int lanes_per_cu, bool schnorr, const bjj::SetArgs& A, const uint32_t* idx, const uint8_t* r,
                       const uint8_t* s, const uint8_t* msg, size_t n, uint8_t* ok);
 
+// k_dlog.hip: small-range discrete logarithms (dlog.hpp).  params: DLOG_PARAM_WORDS words that dlog_setup_table fills for the other
+// launches; slots: 2^(b+2) zeroed 8-byte slots.  dlog_build_table adds the entries it could not place to *d_failed;
+// dlog_check_table adds the violated conditions to d_bad2[0] and the occupied slots to d_bad2[1]; dlog_search runs giant steps
+// s0 .. s1 - 1 for n items (s0 > 0: only items whose ok is BJJ_DLOG_IN_FLIGHT go on; last: this launch ends the call's walk)
+hipError_t dlog_setup_table(hipStream_t st, uint32_t* params, int b, const uint32_t* xy /* 16 words, NULL = B8 */);
+hipError_t dlog_build_table(hipStream_t st, unsigned long long* slots, const uint32_t* params, int b, unsigned long long* d_failed);
+hipError_t dlog_check_table(hipStream_t st, int grid, const unsigned long long* slots, const uint32_t* params, int b, unsigned long long* d_bad2);
+hipError_t dlog_search(hipStream_t st, const unsigned long long* slots, const uint32_t* params, int b, const uint8_t* pts, size_t n,
+                       int range_bits, uint32_t s0, uint32_t s1, bool last, unsigned long long* out_m, uint8_t* ok);
+
 }  // namespace bjjk
