@@ -17,6 +17,22 @@
 #ifndef BJJ_K1_INV_CORE
 #define BJJ_K1_INV_CORE INV_K1
 #endif
+// The overlap form (bjj_k_mul_fixed_base_2x256[_c32]) may start work ahead of need; each part has its own A/B knob
+// (profiles/r10_ab_k1_item_pipeline.txt):
+//   BJJ_K1_PIPE_ITEM    the next item's scalar, digits and first two gathers before the current item's last addition: on,
+//                       +1.8 ... 2.1 % on two streams
+//   BJJ_K1_PIPE_RECORD  phase 2 loads the record of item m-1 before the five multiplications of item m: off, -0.3 ... -0.8 %
+//   BJJ_K1_EARLY_RECORD phase 2's first record is requested before the workgroup inversion, not after its last barrier: off,
+//                       -0.4 ... -0.7 %
+#ifndef BJJ_K1_PIPE_ITEM
+#define BJJ_K1_PIPE_ITEM 1
+#endif
+#ifndef BJJ_K1_PIPE_RECORD
+#define BJJ_K1_PIPE_RECORD 0
+#endif
+#ifndef BJJ_K1_EARLY_RECORD
+#define BJJ_K1_EARLY_RECORD 0
+#endif
 
 // ---------------------------------------------------------------------------
 // init: fixed-base table (layout and recoding: bjj_device.hpp "fixed base").
@@ -52,9 +68,117 @@ __global__ void __launch_bounds__(BJJ_BLOCK) bjj_k_check_fixed_table(const u32* 
 }
 
 
+// ---- the overlap form's split of fixed_base_mul (bjj_device.hpp) and of the epilogue (k_common.hpp) ----------------------
+// fixed_base_mul in two halves, so that K1's loop can begin item k+1 while item k still has its last addition to do: `begin`
+// reduces the scalar (loaded one item earlier still), opens the digit stream and issues the gathers of windows 0 and 1 (both
+// staging areas: they are free once the item before has its last entry in registers); `windows` completes them and runs every
+// addition but the last, whose entry it returns.  The digits, the order of the additions and so the result are fixed_base_mul's.
+struct K1Item {
+  DigitStream ds;
+  bool neg0, neg1;
+};
+template <class G>
+__device__ __forceinline__ K1Item k1_item_begin(const G& g, int W, const U4 (&scalar)[2]) {
+  const u32 raw[8] = {scalar[0].x, scalar[0].y, scalar[0].z, scalar[0].w, scalar[1].x, scalar[1].y, scalar[1].z, scalar[1].w};
+  u32 sc[8];
+  scalar_mod_l(raw, sc, c_K);
+  K1Item it;
+  it.ds = digit_stream(sc, W);
+  typename G::Pending p;
+  g.issue(digit_next(it.ds, it.neg0), p, 0);
+  g.issue(digit_next(it.ds, it.neg1), p, 1);
+  return it;
+}
+template <class G>
+__device__ __forceinline__ void k1_item_windows(const G& g, int nwin, K1Item& it, Ext& acc, Niels& cur) {
+  typename G::Pending p;
+  bool neg;
+  const Niels n0 = niels_cneg_lazy(g.finish(p, 0), it.neg0);
+  acc.X = fr_reduce_weak(fr_sub(n0.ypx, n0.ymx));  // window 0 lifted to (2x' : 2y : 2 : 2x'y), as fixed_base_mul
+  acc.Y = fr_add(n0.ypx, n0.ymx);
+  acc.Z = fr_add(fr_one(), fr_one()); acc.T = fr_add(n0.t2d, fr_zero());
+  BJJ_SCHED_FENCE();
+  cur = niels_cneg_lazy(g.finish(p, 1), it.neg1);
+#pragma unroll 1
+  for (int j = 1; j + 1 < nwin; j++) {
+    g.issue(digit_next(it.ds, neg), p, (j + 1) & 1);
+    acc = ext_madd(acc, cur);
+    BJJ_SCHED_FENCE();
+    cur = niels_cneg_lazy(g.finish(p, (j + 1) & 1), neg);
+  }
+}
+// An item's phase-1 record in registers, and epilogue_finish's arithmetic on it: loading and finishing apart, so that the
+// loads of one record run under the multiplications of another.
+struct K1Record {
+  U4 z[2], p[2], x[2], y[2];   // as loaded: nothing waits for a record before k1_record_finish reads it
+};
+__device__ __forceinline__ void k1_record_load(K1Record& r, const uint8_t* xy_item, const u32* scr_item) {
+  const U4 *s = (const U4*)scr_item, *q = (const U4*)xy_item;
+  r.z[0] = s[0]; r.z[1] = s[1]; r.p[0] = s[2]; r.p[1] = s[3];
+  r.x[0] = q[0]; r.x[1] = q[1]; r.y[0] = q[2]; r.y[1] = q[3];
+}
+__device__ __forceinline__ Fr k1_record_fr(const U4 (&v)[2]) {
+  const u32 w[8] = {v[0].x, v[0].y, v[0].z, v[0].w, v[1].x, v[1].y, v[1].z, v[1].w};
+  return fr_from_words(w);
+}
+template <unsigned FORM>
+__device__ __forceinline__ void k1_record_finish(Fr& inv, uint8_t* out_item, const K1Record& r) {
+  constexpr u32 R1[NL] = {BJJ_N0, BJJ_N1, BJJ_N2, BJJ_N3, BJJ_N4, BJJ_N5, BJJ_N6, BJJ_N7, BJJ_N8};
+  const Fr Z = k1_record_fr(r.z), P = k1_record_fr(r.p), X = k1_record_fr(r.x), Y = k1_record_fr(r.y);
+  Fr zinv = fr_mul(inv, P);               // plain 1/Z
+  inv = fr_mul(inv, Z);
+  Fr c2 = fr_mul(zinv, c_K.FINV);         // plain 1/(Z F)
+  Fr x = fr_cond_sub_kr(fr_mul(X, c2), R1);
+  Fr y = fr_cond_sub_kr(fr_mul(Y, zinv), R1);
+  u32 w[8];
+  if (FORM & EPI_COMPRESS) {
+    fr_to_words(y, w);
+    if (plain_gt_halfq(x, c_K)) w[7] |= 0x80000000u;
+    store_w8(out_item, w);
+  } else {
+    fr_to_words(x, w); store_w8(out_item, w);
+    fr_to_words(y, w); store_w8(out_item + 32, w);
+  }
+}
+// epilogue_run for the overlap form.  A lane's items are finished last to first; `stash` is where phase 1 put X, Y (the output
+// itself for the affine form).  The first record is the one this lane stored last in phase 1: with BJJ_K1_EARLY_RECORD its loads
+// are issued behind a wait for those stores and complete under the inversion.
+template <int BLOCK, unsigned FORM>
+__device__ __forceinline__ void k1_epilogue_run(Fr run, size_t n, size_t tid, size_t nthreads, uint8_t* out, const uint8_t* stash,
+                                                const u32* scratch, u32* lds) {
+  constexpr size_t OUT_BYTES = (FORM & EPI_COMPRESS) ? 32 : 64;
+  const size_t cnt = tid < n ? (n - tid + nthreads - 1) / nthreads : 0;
+  K1Record cur;
+  if (BJJ_K1_EARLY_RECORD && cnt) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this lane's phase-1 stores of the same addresses
+    const size_t i = tid + (cnt - 1) * nthreads;
+    k1_record_load(cur, stash + i * 64, scratch + i * 16);
+  }
+  Fr inv = fr_mul(block_invert<BLOCK, BJJ_K1_INV_CORE>(run, lds), fr_one_plain());  // out of Montgomery form once per lane
+  if (!cnt) return;
+  if (!BJJ_K1_EARLY_RECORD) {
+    const size_t i = tid + (cnt - 1) * nthreads;
+    k1_record_load(cur, stash + i * 64, scratch + i * 16);
+  }
+#pragma unroll 1
+  for (size_t m = cnt; m-- > 0;) {
+    const size_t i = tid + m * nthreads;
+    if (BJJ_K1_PIPE_RECORD) {
+      K1Record nxt = cur;
+      if (m) k1_record_load(nxt, stash + (i - nthreads) * 64, scratch + (i - nthreads) * 16);
+      k1_record_finish<FORM>(inv, out + i * OUT_BYTES, cur);
+      cur = nxt;
+    } else {
+      k1_record_finish<FORM>(inv, out + i * OUT_BYTES, cur);
+      if (m) k1_record_load(cur, stash + (i - nthreads) * 64, scratch + (i - nthreads) * 16);
+    }
+  }
+}
+
 // FORM = EPI_AFFINE: out holds 64-byte points and doubles as the phase-1 stash (xy == out); EPI_COMPRESS: out holds 32-byte
 // Point::compress records (src/lib.rs:166-178) and the stash is the scratch set's XY area.
-template <int BLOCK, int NBUF, unsigned FORM = EPI_AFFINE>
+// AHEAD: the overlap form, which starts the next item and the next phase-2 record ahead of need (the knobs above).
+template <int BLOCK, int NBUF, unsigned FORM = EPI_AFFINE, bool AHEAD = false>
 __device__ __forceinline__ void mul_fixed_base_body(const u32* __restrict__ table, int W, int nwin, const uint8_t* __restrict__ scalars,
                                                     size_t n, uint8_t* __restrict__ out, u32* __restrict__ scratch,
                                                     uint8_t* __restrict__ xy = nullptr) {
@@ -64,16 +188,45 @@ __device__ __forceinline__ void mul_fixed_base_body(const u32* __restrict__ tabl
   const size_t nthreads = (size_t)gridDim.x * blockDim.x;
   const int lane = threadIdx.x & 63;
   const GatherCoopLds<NBUF> fb = {table, stage + (threadIdx.x >> 6) * NBUF * FB_STAGE_WORDS, lane};
+  uint8_t* const stash = (FORM & EPI_COMPRESS) ? xy : out;
   Fr run = fr_one();
+  if (AHEAD && BJJ_K1_PIPE_ITEM) {
+    static_assert(!AHEAD || NBUF >= 2, "both gathers of the next item are issued at once");
+    size_t i = tid;
+    if (i - lane < n) {  // wave-uniform, as every branch of this loop: the gathers are cooperative
+      const U4* const sc4 = (const U4*)scalars;
+      U4 raw[2] = {sc4[2 * (i < n ? i : n - 1)], sc4[2 * (i < n ? i : n - 1) + 1]};
+      K1Item it = k1_item_begin(fb, W, raw);
 #pragma unroll 1
-  for (size_t i = tid; i - lane < n; i += nthreads) {  // wave-uniform trip count: the gathers are cooperative
-    const bool valid = i < n;
-    u32 sc[8];
-    load_w8(scalars + (valid ? i : n - 1) * 32, sc);
-    Ext p = fixed_base_mul(fb, W, nwin, sc, c_K);
-    if (valid) epilogue_stash(p, run, ((FORM & EPI_COMPRESS) ? xy : out) + i * 64, scratch + i * 16);
+      for (;;) {
+        const size_t inext = i + nthreads, iload = inext < n ? inext : n - 1;   // a lane without a next item clamps
+        const bool more = inext - lane < n;
+        if (more) { raw[0] = sc4[2 * iload]; raw[1] = sc4[2 * iload + 1]; }    // the next scalar: in flight under this item's windows
+        Ext acc;
+        Niels cur;
+        k1_item_windows(fb, nwin, it, acc, cur);
+        if (more) it = k1_item_begin(fb, W, raw);                               // its first two gathers: under the last addition
+        BJJ_SCHED_FENCE();
+        const Ext p = ext_madd<false>(acc, cur);  // the last window's addition, T not needed by the epilogue
+        if (i < n) epilogue_stash(p, run, stash + i * 64, scratch + i * 16);
+        if (!more) break;
+        i = inext;
+      }
+    }
+  } else {
+#pragma unroll 1
+    for (size_t i = tid; i - lane < n; i += nthreads) {  // wave-uniform trip count: the gathers are cooperative
+      const bool valid = i < n;
+      u32 sc[8];
+      load_w8(scalars + (valid ? i : n - 1) * 32, sc);
+      Ext p = fixed_base_mul(fb, W, nwin, sc, c_K);
+      if (valid) epilogue_stash(p, run, stash + i * 64, scratch + i * 16);
+    }
   }
-  epilogue_run<BLOCK, FORM, BJJ_K1_INV_CORE>(run, n, tid, nthreads, out, scratch, lds, xy);
+  if (AHEAD && (BJJ_K1_PIPE_RECORD || BJJ_K1_EARLY_RECORD))
+    k1_epilogue_run<BLOCK, FORM>(run, n, tid, nthreads, out, stash, scratch, lds);
+  else
+    epilogue_run<BLOCK, FORM, BJJ_K1_INV_CORE>(run, n, tid, nthreads, out, scratch, lds, xy);
 }
 // Two shapes of the same kernel:
 //  * bjj_k_mul_fixed_base: ONE workgroup of BJJ_K1_BLOCK = 512 lanes per CU (2 waves per SIMD, two staging areas per wave,
@@ -121,7 +274,7 @@ __global__ void __launch_bounds__(BJJ_EPI_BLOCK, 1) bjj_k_mul_fixed_base_scan(co
 __global__ void __launch_bounds__(256, 2) bjj_k_mul_fixed_base_2x256(const u32* __restrict__ table, int W, int nwin,
                                                                     const uint8_t* __restrict__ scalars, size_t n,
                                                                     uint8_t* __restrict__ out, u32* __restrict__ scratch) {
-  mul_fixed_base_body<256, 2>(table, W, nwin, scalars, n, out, scratch);
+  mul_fixed_base_body<256, 2, EPI_AFFINE, true>(table, W, nwin, scalars, n, out, scratch);
 }
 // ---- the same three kernels with Point::compress fused into the epilogue (src/lib.rs:166-178): 32 bytes per result instead of 64.
 // `sk.public().compress()` is what a key server ships, and the host-pointer form of K1 is bound by the copy-out (64 MB of
@@ -136,7 +289,7 @@ __global__ void __launch_bounds__(256, 2) bjj_k_mul_fixed_base_2x256_c32(const u
                                                                         const uint8_t* __restrict__ scalars, size_t n,
                                                                         uint8_t* __restrict__ out32, u32* __restrict__ scratch,
                                                                         uint8_t* __restrict__ xy) {
-  mul_fixed_base_body<256, 2, EPI_COMPRESS>(table, W, nwin, scalars, n, out32, scratch, xy);
+  mul_fixed_base_body<256, 2, EPI_COMPRESS, true>(table, W, nwin, scalars, n, out32, scratch, xy);
 }
 __global__ void __launch_bounds__(BJJ_EPI_BLOCK, 1) bjj_k_mul_fixed_base_scan_c32(const u32* __restrict__ table, int W, int nwin,
                                                                             const uint8_t* __restrict__ scalars, size_t n,
