@@ -10,5 +10,6 @@ from .api import (  # noqa: F401
     Q, B8, SUBORDER, BjjError, Context, MultiContext, Point, PointProjective, Signature, default_context,
     mul_scalar_batch, mul_fixed_base_batch, poseidon5_batch, verify_batch, verify, point_add_batch,
     decompress_point, decompress_signature, PrivateKey, verify_schnorr, new_key, msm, msm_batch, FixedBase, SignerSet, DlogTable,
+    point_sum,
 )
 from ._lib import LIB_PATH, EXPORTED_SYMBOLS, BJJ_WINDOW_AUTO as WINDOW_AUTO  # noqa: F401

@@ -62,6 +62,8 @@ DLOG_SYMBOLS = ("bjj_dlog_table_create", "bjj_dlog_table_free", "bjj_dlog_table_
                 "bjj_dlog_max_range_bits", "bjj_dlog", "bjj_dlog_dev")
 BJJ_DLOG_NOT_IN_RANGE, BJJ_DLOG_FOUND, BJJ_DLOG_OFF_CURVE = 0, 1, 2
 BJJ_DLOG_MAX_GIANT_BITS = 16
+# ... and include/bjj_hip_point_sum.h
+POINT_SUM_SYMBOLS = ("bjj_point_sum", "bjj_point_sum_dev")
 
 
 class BjjInfo(ctypes.Structure):
@@ -223,6 +225,8 @@ def load():
     lib.bjj_dlog_max_range_bits.argtypes = [vp]
     lib.bjj_dlog.argtypes = [vp, vp, vp, sz, ci, vp, vp]
     lib.bjj_dlog_dev.argtypes = [vp, vp, vp, sz, ci, vp, vp, vp]
+    lib.bjj_point_sum.argtypes = [vp, vp, vp, sz, vp, sz, vp, vp]
+    lib.bjj_point_sum_dev.argtypes = [vp, vp, vp, sz, vp, sz, vp, vp, vp]
     # multi-GPU
     pd = ctypes.POINTER(ctypes.c_double)
     lib.bjj_multi_init.argtypes = [ctypes.POINTER(ci), ci, ci, ctypes.POINTER(vp)]

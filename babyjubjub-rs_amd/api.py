@@ -330,6 +330,47 @@ class Context:
                  "bjj_msm_batch")
         return out.reshape(m, 64), status
 
+    def point_sum(self, points, offsets, neg=None):
+        """m signed point sums over the CSR segments [offsets[s], offsets[s + 1]) of one point array (bjj_point_sum): returns
+        (out (m, 64) uint8, status (m,) int64).  Term i is subtracted where neg[i] != 0 (-(x, y) = (-x, y)); neg=None adds every
+        term.  out[s] and status[s] are what msm_batch gives with the scalars 1 and 8l - 1: an empty segment is (0, 1) / -1, an
+        off-curve point makes ITS segment (0, 0) with status[s] = its smallest index in `points` -- returned as data, not raised.
+        offsets: m + 1 values, offsets[0] == 0, non-decreasing, offsets[m] == n (BjjError otherwise)."""
+        a = _as_u8(points, 64, "points")
+        n = a.size // 64
+        g = None
+        if neg is not None:
+            g = np.ascontiguousarray(np.asarray(neg).reshape(-1) != 0, dtype=np.uint8)
+            if g.size != n:
+                raise BjjError("point_sum: %d points but %d signs" % (n, g.size))
+        try:
+            off = np.ascontiguousarray(np.asarray(offsets, dtype=np.uint64).reshape(-1))
+        except (OverflowError, ValueError, TypeError) as e:
+            raise BjjError("point_sum: offsets are unsigned 64-bit integers (%s)" % e)
+        if off.size < 1:
+            raise BjjError("point_sum: offsets holds m + 1 values")
+        m = off.size - 1
+        out = np.empty(m * 64, dtype=np.uint8)
+        status = np.empty(m, dtype=np.int64)
+        self._ck(self.lib.bjj_point_sum(self.handle, a.ctypes.data if n else None, g.ctypes.data if g is not None and n else None, n,
+                                        off.ctypes.data, m, out.ctypes.data if m else None, status.ctypes.data if m else None),
+                 "bjj_point_sum")
+        return out.reshape(m, 64), status
+
+    def elgamal_sum(self, c1, c2, offsets, neg=None):
+        """the homomorphic sum of exponential-ElGamal ciphertexts per segment: both components summed over the same segments and
+        signs (point_sum) -> (C1 (m, 64), C2 (m, 64), status (m,)); (C1[s], C2[s]) decrypts to the signed sum of the segment's
+        plaintexts.  status[s]: the smaller non-negative of the two components' status words, or -1."""
+        a = _as_u8(c1, 64, "c1")
+        b = _as_u8(c2, 64, "c2")
+        if b.size != a.size:
+            raise BjjError("elgamal_sum: array lengths disagree")
+        s1, st1 = self.point_sum(a, offsets, neg)
+        s2, st2 = self.point_sum(b, offsets, neg)
+        both = (st1 >= 0) & (st2 >= 0)
+        status = np.where(both, np.minimum(st1, st2), np.maximum(st1, st2))
+        return s1, s2, status
+
     # ---- fixed-base tables for caller-chosen points (include/bjj_hip_bases.h) ----
     def base(self, point, window_bits=0):
         """a reusable fixed-base table for `point` ((x, y) ints, a Point, or a 64-byte record) -> FixedBase (bjj_base_create).
@@ -643,6 +684,13 @@ class Context:
         the segment, or -2 in every word when the (m + 1) uint64 offsets break their contract)"""
         self._ck(self.lib.bjj_msm_batch_dev(self.handle, d_pts, d_scalars, n, d_offsets, m, int(window_bits), d_out, d_first_off_curve,
                                             stream), "bjj_msm_batch_dev")
+
+    def point_sum_dev(self, d_pts, d_neg, n, d_offsets, m, d_out, d_first_off_curve, stream=0):
+        """bjj_point_sum_dev: d_neg = n sign bytes at any address, or None; m 64-byte results and m int64 status words written by
+        the device (-1, the smallest off-curve index of the segment, or -2 in every word when the (m + 1) uint64 offsets break
+        their contract)"""
+        self._ck(self.lib.bjj_point_sum_dev(self.handle, d_pts, d_neg, n, d_offsets, m, d_out, d_first_off_curve, stream),
+                 "bjj_point_sum_dev")
 
     def msm_dev(self, d_pts, d_scalars, n, d_out, d_first_off_curve, window_bits=0, stream=0):
         """bjj_msm_dev: 64-byte result and the int64 status word (-1, or the smallest off-curve index) written by the device"""
@@ -1168,4 +1216,25 @@ def msm_batch(segments, ctx=None):
     for t, st in enumerate(status):
         if st != -1:
             raise BjjError("msm_batch: segment %d: point %d is not on the curve" % (t, int(st) - offsets[t]))
+    return [Point(x, y) for x, y in _ints(out, 2)]
+
+
+def point_sum(segments, ctx=None):
+    """[the sum of a segment's points for every segment] as Points, in one call (bjj_point_sum).  A segment is a list of Points or
+    (x, y) pairs; an item (point, True) is subtracted.  BjjError names the segment and the index inside it of an off-curve point."""
+    pts, neg, offsets = [], [], [0]
+    for points in segments:
+        for q in points:
+            minus = False
+            if isinstance(q, tuple) and len(q) == 2 and isinstance(q[1], bool):
+                q, minus = q
+            pts.append((q.x, q.y) if isinstance(q, Point) else tuple(q))
+            neg.append(1 if minus else 0)
+        offsets.append(len(pts))
+    if len(offsets) == 1:
+        return []
+    out, status = (ctx or default_context()).point_sum(pts, offsets, neg if any(neg) else None)
+    for t, st in enumerate(status):
+        if st != -1:
+            raise BjjError("point_sum: segment %d: point %d is not on the curve" % (t, int(st) - offsets[t]))
     return [Point(x, y) for x, y in _ints(out, 2)]

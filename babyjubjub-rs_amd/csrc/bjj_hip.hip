@@ -41,6 +41,7 @@
 #include "../../include/bjj_hip_signer.h"
 #include "../../include/bjj_hip_signer_set.h"
 #include "../../include/bjj_hip_dlog.h"
+#include "../../include/bjj_hip_point_sum.h"
 #include "bjj_device.hpp"
 #include "bases.hpp"
 #include "signer.hpp"
@@ -2142,6 +2143,7 @@ int bjj_schnorr_verify_set_dev(bjj_ctx* c, const bjj_signer_set* set, const void
 }
 
 #include "bjj_dlog.inc"
+#include "bjj_point_sum.inc"
 
 #pragma GCC visibility pop
 }  // extern "C"

@@ -165,4 +165,16 @@ hipError_t dlog_check_table(hipStream_t st, int grid, const unsigned long long* 
 hipError_t dlog_search(hipStream_t st, const unsigned long long* slots, const uint32_t* params, int b, const uint8_t* pts, size_t n,
                        int range_bits, uint32_t s0, uint32_t s1, bool last, unsigned long long* out_m, uint8_t* ok);
 
+// k_point_sum.hip: bjj_point_sum -- m signed point sums over the CSR segments offsets[0 .. m] of one point array (point_sum.hpp).
+// The scratch of one call is ONE device block laid out by point_sum_layout (byte offsets, 256-B aligned): the offsets-are-bad word
+// and the two entry lists the levels alternate between (two entries per tile).  `neg`: n bytes or nullptr; `out`, `status` as for
+// msm_batch.  m >= 1.
+struct PointSumLayout {
+  int levels;
+  size_t o_flag, o_e0, o_e1, bytes;
+};
+PointSumLayout point_sum_layout(size_t n);
+hipError_t point_sum(hipStream_t st, const PointSumLayout& L, const uint8_t* pts, const uint8_t* neg, size_t n, const uint64_t* offsets,
+                     size_t m, uint8_t* scratch, uint8_t* out, unsigned long long* status);
+
 }  // namespace bjjk
