@@ -64,6 +64,10 @@ BJJ_DLOG_NOT_IN_RANGE, BJJ_DLOG_FOUND, BJJ_DLOG_OFF_CURVE = 0, 1, 2
 BJJ_DLOG_MAX_GIANT_BITS = 16
 # ... and include/bjj_hip_point_sum.h
 POINT_SUM_SYMBOLS = ("bjj_point_sum", "bjj_point_sum_dev")
+# ... and include/bjj_hip_common_scalar.h
+COMMON_SYMBOLS = ("bjj_mul_common", "bjj_mul_common_dev", "bjj_in_subgroup", "bjj_in_subgroup_dev", "bjj_elgamal_decrypt",
+                  "bjj_elgamal_decrypt_dev")
+BJJ_COMMON_OK, BJJ_COMMON_OFF_CURVE = 1, 2
 
 
 class BjjInfo(ctypes.Structure):
@@ -227,6 +231,12 @@ def load():
     lib.bjj_dlog_dev.argtypes = [vp, vp, vp, sz, ci, vp, vp, vp]
     lib.bjj_point_sum.argtypes = [vp, vp, vp, sz, vp, sz, vp, vp]
     lib.bjj_point_sum_dev.argtypes = [vp, vp, vp, sz, vp, sz, vp, vp, vp]
+    lib.bjj_mul_common.argtypes = [vp, vp, vp, vp, ci, sz, vp, vp]
+    lib.bjj_mul_common_dev.argtypes = [vp, vp, vp, vp, ci, sz, vp, vp, vp]
+    lib.bjj_in_subgroup.argtypes = [vp, vp, sz, vp]
+    lib.bjj_in_subgroup_dev.argtypes = [vp, vp, sz, vp, vp]
+    lib.bjj_elgamal_decrypt.argtypes = [vp, vp, vp, vp, vp, sz, ci, vp, vp]
+    lib.bjj_elgamal_decrypt_dev.argtypes = [vp, vp, vp, vp, vp, sz, ci, vp, vp, vp]
     # multi-GPU
     pd = ctypes.POINTER(ctypes.c_double)
     lib.bjj_multi_init.argtypes = [ctypes.POINTER(ci), ci, ci, ctypes.POINTER(vp)]

@@ -548,6 +548,72 @@ class Context:
         t = self.mul_var_base(a, np.tile(_as_u8([int(sk)], 32, "sk"), n))
         return self.dlog(table, self.point_add(b, _negate_x(t)), range_bits)
 
+    # ---- one scalar, many points (include/bjj_hip_common_scalar.h) ----
+    @staticmethod
+    def _scalar32(scalar, name):
+        """one 32-byte little-endian scalar on the host: an int below 2^256 or 32 bytes"""
+        a = _as_u8([int(scalar)] if isinstance(scalar, int) else scalar, 32, name)
+        if a.size != 32:
+            raise BjjError("%s: one 32-byte scalar" % name)
+        return a
+
+    def mul_common(self, scalar, points, add=None, subtract=False):
+        """out[i] = add[i] + scalar * points[i] (subtract: add[i] - scalar * points[i]; add=None: the identity) with ONE scalar for
+        the call -> (out: (n, 64) uint8, ok: (n,) uint8).  ok 1 = computed, 2 = points[i] or add[i] is not on the curve and
+        out[i] = (0, 0) (bjj_mul_common).  Not constant time in the scalar."""
+        k = self._scalar32(scalar, "scalar")
+        p = _as_u8(points, 64, "points")
+        n = p.size // 64
+        a = None if add is None else _as_u8(add, 64, "add")
+        if a is not None and a.size != p.size:
+            raise BjjError("mul_common: array lengths disagree")
+        out = np.empty(n * 64, dtype=np.uint8)
+        ok = np.empty(n, dtype=np.uint8)
+        self._ck(self.lib.bjj_mul_common(self.handle, k.ctypes.data, p.ctypes.data, None if a is None else a.ctypes.data, 1 if subtract else 0,
+                                         n, out.ctypes.data, ok.ctypes.data), "bjj_mul_common")
+        return out.reshape(n, 64), ok
+
+    def mul_common_dev(self, scalar, d_pts, d_add, n, d_out, d_ok, subtract=False, stream=0):
+        """bjj_mul_common_dev: the scalar on the HOST (int or 32 bytes, read before the call returns); d_add = None for no addend;
+        d_out = n 64-byte records, d_ok = n bytes, on the device"""
+        k = self._scalar32(scalar, "scalar")
+        self._ck(self.lib.bjj_mul_common_dev(self.handle, k.ctypes.data, d_pts, d_add, 1 if subtract else 0, n, d_out, d_ok, stream),
+                 "bjj_mul_common_dev")
+
+    def in_subgroup(self, points):
+        """l * points[i] == identity -> ok: (n,) uint8: 1 = in the prime-order subgroup, 0 = on the curve but not in it, 2 = not on
+        the curve (bjj_in_subgroup)"""
+        p = _as_u8(points, 64, "points")
+        n = p.size // 64
+        ok = np.empty(n, dtype=np.uint8)
+        self._ck(self.lib.bjj_in_subgroup(self.handle, p.ctypes.data, n, ok.ctypes.data), "bjj_in_subgroup")
+        return ok
+
+    def in_subgroup_dev(self, d_pts, n, d_ok, stream=0):
+        self._ck(self.lib.bjj_in_subgroup_dev(self.handle, d_pts, n, d_ok, stream), "bjj_in_subgroup_dev")
+
+    def decrypt(self, table, sk, c1, c2, range_bits):
+        """exponential ElGamal in one call: (m, ok) as dlog() for M = c2 - sk * c1 (bjj_elgamal_decrypt); elgamal_decrypt() is
+        the same result by four calls"""
+        h = self._dlog_handle(table, "decrypt")
+        k = self._scalar32(sk, "sk")
+        a = _as_u8(c1, 64, "c1")
+        b = _as_u8(c2, 64, "c2")
+        n = a.size // 64
+        if b.size != a.size:
+            raise BjjError("decrypt: array lengths disagree")
+        m = np.empty(n, dtype=np.uint64)
+        ok = np.empty(n, dtype=np.uint8)
+        self._ck(self.lib.bjj_elgamal_decrypt(self.handle, h, k.ctypes.data, a.ctypes.data, b.ctypes.data, n, int(range_bits), m.ctypes.data,
+                                              ok.ctypes.data), "bjj_elgamal_decrypt")
+        return m, ok
+
+    def decrypt_dev(self, table, sk, d_c1, d_c2, n, range_bits, d_out_m, d_ok, stream=0):
+        """bjj_elgamal_decrypt_dev: sk on the HOST; d_c1, d_c2 = n 64-byte records, d_out_m = n uint64, d_ok = n bytes, on the device"""
+        k = self._scalar32(sk, "sk")
+        self._ck(self.lib.bjj_elgamal_decrypt_dev(self.handle, self._dlog_handle(table, "decrypt_dev"), k.ctypes.data, d_c1, d_c2, n,
+                                                  int(range_bits), d_out_m, d_ok, stream), "bjj_elgamal_decrypt_dev")
+
     def set_signer_constant_time(self, on=True):
         """signer hardening: public_keys / sign / sign_schnorr scan a small 4-bit table instead of indexing the big one
         with secret digits -- no secret-dependent address or branch; bit-identical results, ~2x slower sign"""

@@ -42,11 +42,13 @@
 #include "../../include/bjj_hip_signer_set.h"
 #include "../../include/bjj_hip_dlog.h"
 #include "../../include/bjj_hip_point_sum.h"
+#include "../../include/bjj_hip_common_scalar.h"
 #include "bjj_device.hpp"
 #include "bases.hpp"
 #include "signer.hpp"
 #include "signer_set.hpp"
 #include "dlog.hpp"
+#include "common_scalar.hpp"
 #include "bjj_launch.hpp"
 #include "msm.hpp"
 #include "copy_pool.hpp"
@@ -168,6 +170,7 @@ struct ScratchSet {
   DevBlock<uint8_t> xy;        // K1 with compressed output: n * 64 B, the phase-1 stash of X, Y (the 32-byte output slot cannot hold it)
   DevBlock<uint8_t> msm;       // bjj_msm: one block per call laid out by bjjk::msm_layout (+ the host form's copies of the inputs)
   DevBlock<uint8_t> bases_io;  // bjj_mul_bases, host form: the t scalar arrays and the results of one call (wiped: ElGamal's r passes through)
+  DevBlock<uint8_t> common_m;  // bjj_elgamal_decrypt: n * 64 B, M = C2 - sk * C1 between the shared-scalar launch and the logarithm's
   // Ordering of the set: every call that uses it records `ev_last` on its stream after enqueueing, and a call on a
   // DIFFERENT stream first makes its stream wait for it.  Calls return before the work runs, so "serialised by the
   // caller" alone would not order execution.
@@ -228,6 +231,7 @@ static uint64_t dlog_launch_steps_from_env() {
   }
   return v;
 }
+static int common_form_from_env();   // bjj_common_scalar.inc
 struct bjj_ctx {
   int device = 0;
   int cus = 0;
@@ -245,6 +249,8 @@ struct bjj_ctx {
   std::vector<bjj_signer_set*> user_sets;   // the sets bjj_signer_set_create made and bjj_signer_set_free has not released yet
   std::vector<bjj_dlog_table*> user_dlogs;  // the tables bjj_dlog_table_create made and bjj_dlog_table_free has not released yet
   uint64_t dlog_launch_steps = 0;           // giant steps one launch of bjj_dlog performs at most, over all its items (BJJ_DLOG_LAUNCH_STEPS)
+  int common_form = -1;          // one scalar, many points: -1 = per call by the multiplication count, 0 = table-free, 1 = table (BJJ_COMMON_FORM)
+  int last_common_form = -1;
   int verify_mode = -1;          // -1 = per call (persistent waves for one launch > 2^21 items that runs alone, groups otherwise), 0 / 1 = forced (BJJ_VERIFY_DISPATCH)
   int k2_variant = -1;           // -1 = per call (tiles for a launch that runs alone, grid-strided while another is in flight), 0 / 1 = forced (BJJ_K2_VARIANT)
   int k1_variant = -1;           // -1 = per call (two-workgroup shape while another launch of the context is in flight), 0 / 1 = forced (BJJ_K1_VARIANT)
@@ -607,6 +613,7 @@ int bjj_init(int device, int window_bits, bjj_ctx** out_ctx) {
   c->lanes_signer = bjjk::signer_lanes_per_cu();
   c->lanes_set = bjjk::set_lanes_per_cu();
   c->dlog_launch_steps = dlog_launch_steps_from_env();
+  c->common_form = common_form_from_env();
   if (const char* e = getenv("BJJ_VERIFY_DISPATCH")) {
     if (e[0] == '0' || e[0] == '1') c->verify_mode = e[0] - '0';
   }
@@ -644,6 +651,8 @@ int bjj_init(int device, int window_bits, bjj_ctx** out_ctx) {
   }
   c->occ_vb_scan = bjjk::occ_var_base_scan();
   c->lanes_var = bjjk::var_base_lanes_per_cu();
+  // the table form of the shared-scalar kernel pops K2's slot queue: it must not have more workgroups resident than K2 has slots
+  if (bjjk::common_scalar_table_blocks_per_cu() * bjjk::var_base_block() > c->lanes_var) c->common_form = CS_FORM_NAF;
   c->occ_poseidon = bjjk::occ_poseidon5();
   c->occ_verify = bjjk::occ_verify();
   c->occ_scan = bjjk::occ_verify_scan();
@@ -2144,6 +2153,7 @@ int bjj_schnorr_verify_set_dev(bjj_ctx* c, const bjj_signer_set* set, const void
 
 #include "bjj_dlog.inc"
 #include "bjj_point_sum.inc"
+#include "bjj_common_scalar.inc"
 
 #pragma GCC visibility pop
 }  // extern "C"

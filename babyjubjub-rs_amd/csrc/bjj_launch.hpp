@@ -20,6 +20,7 @@
 namespace bjj { struct BasesArgs; }   // bases.hpp: the per-base descriptors of bjj_k_mul_bases
 namespace bjj { struct SignerArgs; }  // signer.hpp: the two tables and the point of bjj_k_verify_signer
 namespace bjj { struct SetArgs; }     // signer_set.hpp: the set's tables and keys, the B8 table (bjj_k_verify_set)
+namespace bjj { struct CsDigits; }    // common_scalar.hpp: the recoded scalar of bjj_k_mul_common, by value in the kernel arguments
 
 namespace bjjk {
 
@@ -176,5 +177,15 @@ struct PointSumLayout {
 PointSumLayout point_sum_layout(size_t n);
 hipError_t point_sum(hipStream_t st, const PointSumLayout& L, const uint8_t* pts, const uint8_t* neg, size_t n, const uint64_t* offsets,
                      size_t m, uint8_t* scratch, uint8_t* out, unsigned long long* status);
+
+// k_common_scalar.hip: one scalar, many points (common_scalar.hpp) -- out[i] = add[i] + (the digits D) * pts[i], one 256-item tile per
+// workgroup.  form: CS_FORM_NAF (no table, no slot queue) or CS_FORM_TABLE (vb_tables / slotq / slot_cap as for K2's tiles).
+//   COMMON_POINT     add may be nullptr; out: n * 64 bytes, ok: n bytes (1, or 2 and (0, 0) for an off-curve item); scratch: n * 64 bytes
+//   COMMON_SUBGROUP  ok: n bytes (1 = the product is the identity, 0 = it is not, 2 = off the curve); no add, out or scratch
+//   COMMON_DECRYPT   the point form with add != nullptr and no ok
+enum { COMMON_POINT = 0, COMMON_SUBGROUP = 1, COMMON_DECRYPT = 2 };
+int common_scalar_table_blocks_per_cu();
+hipError_t mul_common(hipStream_t st, int form, int epi, const bjj::CsDigits& D, const uint8_t* pts, const uint8_t* add, size_t n, uint8_t* out,
+                      uint8_t* ok, uint32_t* scratch, uint32_t* vb_tables, uint32_t* slotq, uint32_t slot_cap);
 
 }  // namespace bjjk
