@@ -90,6 +90,42 @@ def test_window_counts_and_patterns():
             assert v < ORDER8 and v & ((1 << W) - 1) == d and v >> (W * (base_windows(W) - 3)) != 0
 
 
+def signed_digits(v, W, nwin):
+    """digit_next of csrc/bjj_device.hpp in plain integers: u = low W bits + carry; u > 2^(W-1) becomes u - 2^W and carries one
+    into the next window (u == 2^W is digit 0 with a carry) -> (the nwin digits, the carry that leaves the top window)"""
+    digits, carry = [], 0
+    for _ in range(nwin):
+        u = (v & ((1 << W) - 1)) + carry
+        carry = 1 if u > 1 << (W - 1) else 0
+        digits.append(u - (carry << W))
+        v >>= W
+    assert v == 0                                          # every bit of the scalar lies inside the windows
+    return digits, carry
+
+
+@pytest.mark.parametrize("W", range(4, 29))
+def test_signed_recoding_fits_the_windows_of_every_width(W):
+    """the argument of csrc/bases.hpp, lines 5-9, for every width bjj_base_create accepts: a scalar below 8l < 2^254 recoded over
+    base_windows(W) = ceil(255 / W) windows sums back to itself, its top digit is non-negative and no carry leaves the top window;
+    every digit is a slot of the window, |d| <= 2^(W-1).  tests/bases_emul prints results, not digits, so the shipped digit_next
+    is held against this model through its results only (test_tables_and_results_match_the_oracle, W = 4, 5, 12)."""
+    from bases_cases import ORDER8, base_windows, pattern
+    nwin = base_windows(W)
+    assert nwin * W >= 255 > (nwin - 1) * W
+    half = 1 << (W - 1)
+    rng = np.random.default_rng(0xD161 + W)
+    seeded = [int.from_bytes(rng.bytes(32), "little") % ORDER8 for _ in range(1000)]
+    for v in [ORDER8 - 1, pattern(W, half), pattern(W, half + 1)] + seeded:
+        assert v < ORDER8
+        digits, carry = signed_digits(v, W, nwin)
+        assert sum(d << (W * j) for j, d in enumerate(digits)) == v, (W, hex(v))
+        assert carry == 0 and digits[-1] >= 0, (W, hex(v), digits[-1])
+        assert all(-half <= d <= half for d in digits), (W, hex(v))
+    assert all(d == half for d in signed_digits(pattern(W, half), W, nwin)[0] if d)            # no carry anywhere
+    neg = signed_digits(pattern(W, half + 1), W, nwin)[0]
+    assert neg[0] == -(half - 1) and sum(d < 0 for d in neg) >= nwin - 2                         # the carry runs through every window
+
+
 def test_tables_and_results_match_the_oracle(inputs, expected, tmp_path):
     exe = os.path.join(ROOT, "tests", "bases_emul", "bases_emul")
     c = _build(exe, False)

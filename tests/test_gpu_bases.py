@@ -188,6 +188,27 @@ def test_base_check_and_info(gpu_ctx, points, tables):
         d.close()
 
 
+@pytest.mark.parametrize("W", [5, 15, 17, 20])
+def test_width_sweep_against_oracle(gpu_ctx, oracle, points, W):
+    """widths that divide 255 (5, 15, 17: the top window is a full W bits wide, of which a scalar below 8l < 2^254 fills W - 1) and
+    one above every other caller's table in the suite (20: 13 windows of 2^19 + 1 entries, 0.87 GB); tests/test_bases_host.py
+    holds the recoding argument for every width in plain integers"""
+    n = 257
+    nwin = -(-255 // W)
+    assert nwin == base_windows(W) and (255 % W == 0) == (W != 20)
+    sc = scalar_array(n, (W,), 0x51DE + W)
+    want = oracle.mul_var_base(rep(points["k1"], n), sc)
+    base = gpu_ctx.base(points["k1"], W)
+    try:
+        assert base.info() == (W, nwin, ((1 << (W - 1)) + 1) * nwin * 128)
+        assert base.check() == 0
+        got = base.mul(sc)
+        bad = np.nonzero((got != want).any(axis=1))[0]
+        assert got.shape == (n, 64) and bad.size == 0, (W, bad[:8].tolist())
+    finally:
+        base.close()
+
+
 # ---- 5 ---------------------------------------------------------------------------------------------------------------------------
 def test_rejections(gpu_ctx, points, tables, S):
     import torch
