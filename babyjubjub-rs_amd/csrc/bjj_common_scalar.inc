@@ -17,8 +17,13 @@ static const Consts& common_host_consts() {
   }();
   return K;
 }
-// The scalar is read, reduced mod 8l and recoded here, before the call returns; what is left of it on the stack is wiped.
-struct CommonPlan { CsDigits D; int form; };
+// The scalar is read, reduced mod 8l and recoded here, before the call returns; what is left of it on the stack is wiped -- the
+// plan by its destructor, on every return path of the function that holds it.
+struct CommonPlan {
+  CsDigits D;
+  int form;
+  ~CommonPlan() { secure_bzero(this, sizeof(*this)); }
+};
 static void common_plan(const bjj_ctx* c, const uint8_t* scalar, bool negate, CommonPlan* P) {
   u32 raw[8];
   memcpy(raw, scalar, 32);
@@ -58,7 +63,6 @@ static int mul_common_dev_impl(bjj_ctx* c, const uint8_t* scalar, const void* d_
   common_plan(c, scalar, subtract != 0, &P);
   SET_ENTER(c, stream, n, false);
   LAUNCHCK_S(common_enqueue(c, S, st, P, epi, (const uint8_t*)d_pts, (const uint8_t*)d_add, n, (uint8_t*)d_out, (uint8_t*)d_ok), who);
-  secure_bzero(&P, sizeof(P));
   SET_LEAVE(c);
 }
 int bjj_mul_common_dev(bjj_ctx* c, const uint8_t* scalar, const void* d_pts_xy, const void* d_add_xy, int subtract, size_t n, void* d_out_xy,
@@ -76,7 +80,7 @@ int bjj_in_subgroup_dev(bjj_ctx* c, const void* d_pts_xy, size_t n, void* d_ok, 
   common_l_bytes(l);
   return mul_common_dev_impl(c, l, d_pts_xy, nullptr, 0, n, nullptr, d_ok, stream, bjjk::COMMON_SUBGROUP, "bjj_in_subgroup_dev");
 }
-// Synchronous host forms: one copy in per array into the set's block, the launch, one copy out per output array.
+// Synchronous host forms (Staged): the points and the addends (when given), then the results (but for the subgroup check) and the verdicts
 static int mul_common_host_impl(bjj_ctx* c, const uint8_t* scalar, const uint8_t* pts, const uint8_t* add, int subtract, size_t n, uint8_t* out,
                                 uint8_t* ok, int epi, const char* who) {
   { int rc = common_check(c, scalar, n, who); if (rc) return rc; }
@@ -85,22 +89,13 @@ static int mul_common_host_impl(bjj_ctx* c, const uint8_t* scalar, const uint8_t
   if (!pts || !ok || (point && !out)) return set_err(BJJ_E_INVALID, std::string(who) + ": NULL buffer");
   CommonPlan P;
   common_plan(c, scalar, subtract != 0, &P);
-  void* const stream = nullptr;   // the context's stream
-  SET_ENTER(c, stream, n, false);
-  const size_t o_add = up256(n * 64), o_out = o_add + up256(add ? n * 64 : 0), o_ok = o_out + up256(point ? n * 64 : 0);
-  if (S->bases_io.grow(o_ok + n) != hipSuccess) {
-    (void)hipGetLastError();
-    return set_err(BJJ_E_NOMEM, std::string(who) + ": cannot allocate " + std::to_string((o_ok + n) >> 20) + " MB of device staging");
-  }
-  uint8_t* blk = S->bases_io;
-  HIPCK(hipMemcpyAsync(blk, pts, n * 64, hipMemcpyHostToDevice, st));
-  if (add) HIPCK(hipMemcpyAsync(blk + o_add, add, n * 64, hipMemcpyHostToDevice, st));
-  LAUNCHCK_S(common_enqueue(c, S, st, P, epi, blk, add ? blk + o_add : nullptr, n, point ? blk + o_out : nullptr, blk + o_ok), who);
-  secure_bzero(&P, sizeof(P));
-  if (point) HIPCK(hipMemcpyAsync(out, blk + o_out, n * 64, hipMemcpyDeviceToHost, st));
-  HIPCK(hipMemcpyAsync(ok, blk + o_ok, n, hipMemcpyDeviceToHost, st));
-  { int rc = set_leave(c, S, st); if (rc) return rc; }
-  HIPCK(hipStreamSynchronize(st));
+  ENTER_DEVICE(c->device);
+  Staged G(c, who);
+  { int rc = ensure_scratch(c, G.S, n); if (rc) return rc; }
+  const int i_pts = G.in(pts, n, 64), i_add = G.in_opt(add, n, 64), i_out = G.out_opt(point ? out : nullptr, n, 64), i_ok = G.out(ok, n, 1);
+  { int rc = G.begin(G.S->bases_io, "device staging"); if (rc) return rc; }
+  LAUNCHCK_S(common_enqueue(c, G.S, G.st, P, epi, G.dev(i_pts), G.dev(i_add), n, G.dev(i_out), G.dev(i_ok)), who);
+  { int rc = G.finish(); if (rc) return rc; }
   return ctx_check_slot_queues(c, who);
 }
 int bjj_mul_common(bjj_ctx* c, const uint8_t* scalar, const uint8_t* pts_xy, const uint8_t* add_xy, int subtract, size_t n, uint8_t* out_xy,
@@ -136,7 +131,6 @@ int bjj_elgamal_decrypt_dev(bjj_ctx* c, const bjj_dlog_table* t, const uint8_t* 
   SET_ENTER(c, stream, n, false);
   { int rc = decrypt_block(S, n, who); if (rc) return rc; }
   LAUNCHCK_S(common_enqueue(c, S, st, P, bjjk::COMMON_DECRYPT, (const uint8_t*)d_c1_xy, (const uint8_t*)d_c2_xy, n, S->common_m, nullptr), who);
-  secure_bzero(&P, sizeof(P));
   LAUNCHCK_S(dlog_enqueue(c, st, t, S->common_m, n, range_bits, (unsigned long long*)d_out_m, (uint8_t*)d_ok), who);
   SET_LEAVE(c);
 }
@@ -148,23 +142,14 @@ int bjj_elgamal_decrypt(bjj_ctx* c, const bjj_dlog_table* t, const uint8_t* sk, 
   if (!c1_xy || !c2_xy || !out_m || !ok) return set_err(BJJ_E_INVALID, std::string(who) + ": NULL buffer");
   CommonPlan P;
   common_plan(c, sk, true, &P);
-  void* const stream = nullptr;   // the context's stream
-  SET_ENTER(c, stream, n, false);
-  { int rc = decrypt_block(S, n, who); if (rc) return rc; }
-  const size_t o_c2 = up256(n * 64), o_m = o_c2 + up256(n * 64), o_ok = o_m + up256(n * 8);
-  if (S->bases_io.grow(o_ok + n) != hipSuccess) {
-    (void)hipGetLastError();
-    return set_err(BJJ_E_NOMEM, std::string(who) + ": cannot allocate " + std::to_string((o_ok + n) >> 20) + " MB of device staging");
-  }
-  uint8_t* blk = S->bases_io;
-  HIPCK(hipMemcpyAsync(blk, c1_xy, n * 64, hipMemcpyHostToDevice, st));
-  HIPCK(hipMemcpyAsync(blk + o_c2, c2_xy, n * 64, hipMemcpyHostToDevice, st));
-  LAUNCHCK_S(common_enqueue(c, S, st, P, bjjk::COMMON_DECRYPT, blk, blk + o_c2, n, S->common_m, nullptr), who);
-  secure_bzero(&P, sizeof(P));
-  LAUNCHCK_S(dlog_enqueue(c, st, t, S->common_m, n, range_bits, (unsigned long long*)(blk + o_m), blk + o_ok), who);
-  HIPCK(hipMemcpyAsync(out_m, blk + o_m, n * 8, hipMemcpyDeviceToHost, st));
-  HIPCK(hipMemcpyAsync(ok, blk + o_ok, n, hipMemcpyDeviceToHost, st));
-  { int rc = set_leave(c, S, st); if (rc) return rc; }
-  HIPCK(hipStreamSynchronize(st));
+  ENTER_DEVICE(c->device);
+  Staged G(c, who);   // C1 and C2, then the logarithms and the verdicts
+  { int rc = ensure_scratch(c, G.S, n); if (rc) return rc; }
+  { int rc = decrypt_block(G.S, n, who); if (rc) return rc; }
+  const int i_c1 = G.in(c1_xy, n, 64), i_c2 = G.in(c2_xy, n, 64), i_m = G.out(out_m, n, 8), i_ok = G.out(ok, n, 1);
+  { int rc = G.begin(G.S->bases_io, "device staging"); if (rc) return rc; }
+  LAUNCHCK_S(common_enqueue(c, G.S, G.st, P, bjjk::COMMON_DECRYPT, G.dev(i_c1), G.dev(i_c2), n, G.S->common_m, nullptr), who);
+  LAUNCHCK_S(dlog_enqueue(c, G.st, t, G.S->common_m, n, range_bits, (unsigned long long*)G.dev(i_m), G.dev(i_ok)), who);
+  { int rc = G.finish(); if (rc) return rc; }
   return ctx_check_slot_queues(c, who);
 }

@@ -3,21 +3,13 @@
 // for 2^20 items against 120.4 .. 127.0 ms at 22 bits, for 512 MiB instead of 128 (DESIGN.md section 13, profiles/dlog.txt).
 #define BJJ_DLOG_DEFAULT_BABY_BITS 24
 static_assert(BJJ_DLOG_MAX_GIANT_BITS == BJJ_DLOG_GIANT_BITS, "include/bjj_hip_dlog.h and dlog.hpp disagree");
-static bool dlog_of_ctx(const bjj_ctx* c, const bjj_dlog_table* t) {
-  for (const bjj_dlog_table* k : c->user_dlogs) if (k == t) return true;
-  return false;
-}
 // violated conditions of the finished table: entries not found under their own y, slots with a value out of range, and one more
 // when the occupied slots do not number 2^b + 1
 static int dlog_run_check(bjj_ctx* c, const bjj_dlog_table* t, unsigned long long* bad, const char* who) {
-  DevBlock<unsigned long long> d_bad;
   unsigned long long h[2] = {0, 0};
-  hipError_t e = d_bad.grow(2 * sizeof(unsigned long long), NO_WAIT);
-  if (e == hipSuccess) e = hipMemsetAsync(d_bad, 0, 2 * sizeof(unsigned long long), c->stream);
-  if (e == hipSuccess) e = bjjk::dlog_check_table(c->stream, c->cus * 8, t->slots, t->params, t->b, d_bad);
-  if (e == hipSuccess) e = hipMemcpyAsync(h, d_bad, sizeof(h), hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess) return set_err(BJJ_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
+  { int rc = device_counters(c, 2, h, who, [&](unsigned long long* d_bad) {
+      return bjjk::dlog_check_table(c->stream, c->cus * 8, t->slots, t->params, t->b, d_bad); });
+    if (rc) return rc; }
   *bad = h[0] + (h[1] != dlog_entries(t->b) ? 1ull : 0ull);
   return BJJ_OK;
 }
@@ -70,19 +62,17 @@ int bjj_dlog_table_create(bjj_ctx* c, const uint8_t* point_xy, int baby_bits, bj
     delete t;
     return set_err(BJJ_E_HIP, "bjj_dlog_table_create: the table failed its self-check (" + std::to_string(bad + failed) + " conditions)");
   }
-  try { c->user_dlogs.push_back(t); } catch (...) { delete t; return set_err(BJJ_E_NOMEM, "bjj_dlog_table_create: out of host memory"); }
+  try { c->user_dlogs.add(t); } catch (...) { delete t; return set_err(BJJ_E_NOMEM, "bjj_dlog_table_create: out of host memory"); }
   *out = t;
   return BJJ_OK;
 }
 int bjj_dlog_table_free(bjj_ctx* c, bjj_dlog_table* t) {
   CHECK_CTX(c, "bjj_dlog_table_free");
   if (!t) return BJJ_OK;
-  if (!dlog_of_ctx(c, t)) return set_err(BJJ_E_INVALID, "bjj_dlog_table_free: not a table of this context");
+  if (!c->user_dlogs.owns(t)) return set_err(BJJ_E_INVALID, "bjj_dlog_table_free: not a table of this context");
   ENTER_DEVICE(c->device);
   { int rc = ctx_wait_enqueued(c); if (rc) return rc; }   // launches that read the table
-  for (size_t i = 0; i < c->user_dlogs.size(); i++)
-    if (c->user_dlogs[i] == t) { c->user_dlogs.erase(c->user_dlogs.begin() + (long)i); break; }
-  delete t;
+  c->user_dlogs.drop(t);
   return BJJ_OK;
 }
 int bjj_dlog_table_info(const bjj_dlog_table* t, int* baby_bits, uint64_t* entries, uint64_t* table_bytes) {
@@ -95,7 +85,7 @@ int bjj_dlog_table_info(const bjj_dlog_table* t, int* baby_bits, uint64_t* entri
 int bjj_dlog_table_check(bjj_ctx* c, const bjj_dlog_table* t, uint64_t* n_bad) {
   CHECK_CTX(c, "bjj_dlog_table_check");
   if (!t || !n_bad) return set_err(BJJ_E_INVALID, "bjj_dlog_table_check: NULL argument");
-  if (!dlog_of_ctx(c, t)) return set_err(BJJ_E_INVALID, "bjj_dlog_table_check: not a table of this context");
+  if (!c->user_dlogs.owns(t)) return set_err(BJJ_E_INVALID, "bjj_dlog_table_check: not a table of this context");
   ENTER_DEVICE(c->device);
   unsigned long long bad = 0;
   { int rc = dlog_run_check(c, t, &bad, "bjj_dlog_table_check"); if (rc) return rc; }
@@ -115,7 +105,7 @@ static int dlog_check_args(bjj_ctx* c, const bjj_dlog_table* t, size_t n, int ra
   if (!t) return set_err(BJJ_E_INVALID, std::string(who) + ": table is NULL");
   if (range_bits < 1 || range_bits > dlog_max_range_bits(BJJ_DLOG_MAX_BABY_BITS))
     return set_err(BJJ_E_INVALID, std::string(who) + ": range_bits must be 1 .. baby_bits + 1 + BJJ_DLOG_MAX_GIANT_BITS");
-  if (!dlog_of_ctx(c, t)) return set_err(BJJ_E_INVALID, std::string(who) + ": table is not a dlog table of this context");
+  if (!c->user_dlogs.owns(t)) return set_err(BJJ_E_INVALID, std::string(who) + ": table is not a dlog table of this context");
   if (range_bits > dlog_max_range_bits(t->b))
     return set_err(BJJ_E_INVALID, std::string(who) + ": range_bits must be 1 .. " + std::to_string(dlog_max_range_bits(t->b)) + " for this table");
   CHECK_N(n);
@@ -156,26 +146,15 @@ int bjj_dlog_dev(bjj_ctx* c, const bjj_dlog_table* t, const void* d_pts_xy, size
   LAUNCHCK_S(dlog_enqueue(c, st, t, (const uint8_t*)d_pts_xy, n, range_bits, (unsigned long long*)d_out_m, (uint8_t*)d_ok), "bjj_dlog_dev");
   DEV_LEAVE(c);
 }
-// Synchronous: the records go to the scratch set's block with one copy (pinned or pageable), the launches, one copy out per array.
+// Synchronous (Staged): the records, then the logarithms and the verdicts
 int bjj_dlog(bjj_ctx* c, const bjj_dlog_table* t, const uint8_t* pts_xy, size_t n, int range_bits, uint64_t* out_m, uint8_t* ok) {
   { int rc = dlog_check_args(c, t, n, range_bits, "bjj_dlog"); if (rc) return rc; }
   if (n == 0) return BJJ_OK;
   if (!pts_xy || !out_m || !ok) return set_err(BJJ_E_INVALID, "bjj_dlog: NULL buffer");
-  hipStream_t st = c->stream;
   ENTER_DEVICE(c->device);
-  ScratchSet* S = pick_set(c, st);
-  const size_t o_m = up256(n * 64), o_ok = o_m + up256(n * 8);
-  if (S->bases_io.grow(o_ok + n) != hipSuccess) {
-    (void)hipGetLastError();
-    return set_err(BJJ_E_NOMEM, "bjj_dlog: cannot allocate " + std::to_string((o_ok + n) >> 20) + " MB of device staging");
-  }
-  { int rc = set_enter(c, S, st); if (rc) return rc; }
-  uint8_t* blk = S->bases_io;
-  HIPCK(hipMemcpyAsync(blk, pts_xy, n * 64, hipMemcpyHostToDevice, st));
-  LAUNCHCK_S(dlog_enqueue(c, st, t, blk, n, range_bits, (unsigned long long*)(blk + o_m), blk + o_ok), "bjj_dlog");
-  HIPCK(hipMemcpyAsync(out_m, blk + o_m, n * 8, hipMemcpyDeviceToHost, st));
-  HIPCK(hipMemcpyAsync(ok, blk + o_ok, n, hipMemcpyDeviceToHost, st));
-  { int rc = set_leave(c, S, st); if (rc) return rc; }
-  HIPCK(hipStreamSynchronize(st));
-  return BJJ_OK;
+  Staged G(c, "bjj_dlog");
+  const int i_pts = G.in(pts_xy, n, 64), i_m = G.out(out_m, n, 8), i_ok = G.out(ok, n, 1);
+  { int rc = G.begin(G.S->bases_io, "device staging"); if (rc) return rc; }
+  LAUNCHCK_S(dlog_enqueue(c, G.st, t, G.dev(i_pts), n, range_bits, (unsigned long long*)G.dev(i_m), G.dev(i_ok)), "bjj_dlog");
+  return G.finish();
 }

@@ -53,6 +53,7 @@
 #include "msm.hpp"
 #include "copy_pool.hpp"
 #include "pipe_plan.hpp"
+#include "stage_plan.hpp"
 
 using namespace bjj;
 
@@ -74,6 +75,9 @@ static const int kAutoWindowBits[] = {28, 26, 23, 21, 16};
 // ===========================================================================
 // context
 // ===========================================================================
+// The error messages concatenate temporaries, and namespace std has default visibility: the library has always exported this weak
+// instantiation.  Instantiated explicitly, so that the list of exported symbols does not depend on how many uses the inliner leaves.
+template std::string std::operator+(std::string&&, std::string&&);
 static thread_local std::string g_err;
 static int set_err(int code, const std::string& msg) { g_err = msg; return code; }
 #define HIPCK(call)                                                                                  \
@@ -168,8 +172,10 @@ struct ScratchSet {
   u32 slot_cap = 0;            // slots per XCD
   DevBlock<uint8_t> codec;     // verify_compressed: n * (64 pk + 64 R + 32 s + 2 flags) bytes; public_keys: the scalar keys (wiped)
   DevBlock<uint8_t> xy;        // K1 with compressed output: n * 64 B, the phase-1 stash of X, Y (the 32-byte output slot cannot hold it)
-  DevBlock<uint8_t> msm;       // bjj_msm: one block per call laid out by bjjk::msm_layout (+ the host form's copies of the inputs)
-  DevBlock<uint8_t> bases_io;  // bjj_mul_bases, host form: the t scalar arrays and the results of one call (wiped: ElGamal's r passes through)
+  // The blocks of the staged host forms (Staged): one call's arrays at the offsets of a StagePlan
+  DevBlock<uint8_t> msm;       // bjj_msm*, bjj_point_sum: the scratch the kernel layout describes (all the _dev forms take); host forms: + offsets, inputs, results
+  DevBlock<uint8_t> bases_io;  // the host forms of bjj_mul_bases, *_verify_signer, *_verify_set, bjj_dlog, bjj_mul_common, bjj_in_subgroup and
+                               // bjj_elgamal_decrypt: inputs, then outputs (wiped: ElGamal's r and the ciphertexts pass through)
   DevBlock<uint8_t> common_m;  // bjj_elgamal_decrypt: n * 64 B, M = C2 - sk * C1 between the shared-scalar launch and the logarithm's
   // Ordering of the set: every call that uses it records `ev_last` on its stream after enqueueing, and a call on a
   // DIFFERENT stream first makes its stream wait for it.  Calls return before the work runs, so "serialised by the
@@ -214,6 +220,18 @@ struct bjj_dlog_table {
   DevBlock<unsigned long long> slots;      // 2^(b+2) slots {tag, j + 1}
   DevBlock<u32> params;                    // DLOG_PARAM_WORDS words: Niels(G), Niels(-2^b G), Niels(-2^(b+1) G), the base's record
 };
+// The handles a context has handed out and not been given back (bjj_base, bjj_signer_set, bjj_dlog_table): the context owns them
+template <typename T>
+struct Handles {
+  std::vector<T*> v;
+  bool owns(const T* h) const { for (const T* k : v) if (k == h) return true; return false; }
+  void add(T* h) { v.push_back(h); }   // may throw: the caller still owns h then
+  void drop(T* h) {                    // forgets and deletes h
+    for (size_t i = 0; i < v.size(); i++) if (v[i] == h) { v.erase(v.begin() + (long)i); break; }
+    delete h;
+  }
+  void clear() { for (T* h : v) delete h; v.clear(); }   // the handles the caller never freed
+};
 // Giant steps ONE launch of bjj_dlog / bjj_dlog_dev performs at most, summed over its items; a longer call is cut into consecutive
 // launches: 2^27 steps fill the chip for 29 ms.  BJJ_DLOG_LAUNCH_STEPS, read once here, lowers or raises it
 // (tests force the cut with it).  Beside it, no launch walks an item further than BJJ_DLOG_LAUNCH_STEPS_PER_ITEM steps -- a workgroup
@@ -244,10 +262,10 @@ struct bjj_ctx {
   int lanes_fixed_2x256 = 512;   // resident lanes per CU of K1's two-workgroup shape
   int lanes_bases = 512;         // resident lanes per CU of bjj_k_mul_bases
   int lanes_signer = 512;        // resident lanes per CU of the bjj_k_*_verify_signer kernels
-  std::vector<bjj_base*> user_bases;   // the tables bjj_base_create made and bjj_base_free has not released yet
+  Handles<bjj_base> user_bases;         // the tables bjj_base_create made and bjj_base_free has not released yet
   int lanes_set = 512;           // resident lanes per CU of the bjj_k_*_verify_set kernels
-  std::vector<bjj_signer_set*> user_sets;   // the sets bjj_signer_set_create made and bjj_signer_set_free has not released yet
-  std::vector<bjj_dlog_table*> user_dlogs;  // the tables bjj_dlog_table_create made and bjj_dlog_table_free has not released yet
+  Handles<bjj_signer_set> user_sets;        // the sets bjj_signer_set_create made and bjj_signer_set_free has not released yet
+  Handles<bjj_dlog_table> user_dlogs;      // the tables bjj_dlog_table_create made and bjj_dlog_table_free has not released yet
   uint64_t dlog_launch_steps = 0;           // giant steps one launch of bjj_dlog performs at most, over all its items (BJJ_DLOG_LAUNCH_STEPS)
   int common_form = -1;          // one scalar, many points: -1 = per call by the multiplication count, 0 = table-free, 1 = table (BJJ_COMMON_FORM)
   int last_common_form = -1;
@@ -533,6 +551,75 @@ static int ensure_xy(ScratchSet* S, size_t n) {     // 64 bytes per item: X, Y o
   return BJJ_OK;
 }
 static bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+// a block of a scratch set holds at least `bytes`; a block this size may well not fit: the set stays usable, without that block
+static int grow_block(DevBlock<uint8_t>& b, size_t bytes, const char* who, const char* noun) {
+  if (b.grow(bytes) == hipSuccess) return BJJ_OK;
+  (void)hipGetLastError();
+  return set_err(BJJ_E_NOMEM, std::string(who) + ": cannot allocate " + std::to_string(bytes >> 20) + " MB of " + noun);
+}
+// ---- the synchronous single-launch host forms --------------------------------------------------------------
+// One staged call on the context's own stream.  The entry declares its arrays in argument order, the inputs first (in / out; *_opt:
+// an array the caller may leave out; *_at: at an offset inside the scratch prefix), and begin() lays them out in ONE block of the
+// stream's scratch set (StagePlan), grows the block, enters the set and enqueues one copy in per array, straight from the caller's
+// memory (pinned or pageable).  The entry then enqueues its launches on dev() pointers -- through the same function as its _dev
+// twin -- and finish() enqueues one copy out per output, leaves the set and waits for the stream.  The block grows BEFORE the set
+// is entered: Block::grow(WAIT_DEVICE) waits for the whole device itself before it frees a block, so the order carries no dependency.
+static_assert(STAGE_MAX_ARRAYS == BJJ_MAX_BASES + 1, "stage_plan.hpp: room for the largest site, bjj_mul_bases");
+struct Staged {
+  bjj_ctx* c;
+  const char* who;
+  hipStream_t st;
+  ScratchSet* S;
+  StagePlan plan;
+  void* host[STAGE_MAX_ARRAYS] = {};
+  bool absent[STAGE_MAX_ARRAYS] = {};
+  uint8_t* blk = nullptr;
+  Staged(bjj_ctx* c_, const char* who_, size_t prefix = 0) : c(c_), who(who_), st(c_->stream), S(pick_set(c_, c_->stream)), plan(prefix) {}
+  int note(int i, const void* h, bool gone = false) { if (i >= 0) { host[i] = const_cast<void*>(h); absent[i] = gone; } return i; }
+  int in(const void* h, size_t count, size_t width) { return note(plan.add(false, count, width), h); }
+  int out(void* h, size_t count, size_t width) { return note(plan.add(true, count, width), h); }
+  int in_opt(const void* h, size_t count, size_t width) { return note(plan.add(false, h ? count : 0, width), h, !h); }
+  int out_opt(void* h, size_t count, size_t width) { return note(plan.add(true, h ? count : 0, width), h, !h); }
+  int in_at(size_t off, const void* h, size_t bytes) { return note(plan.at(false, off, bytes), h); }
+  int out_at(size_t off, void* h, size_t bytes) { return note(plan.at(true, off, bytes), h); }
+  uint8_t* dev(int i) const { return absent[i] ? nullptr : blk + plan.a[i].off; }
+  int copy(bool outputs) {   // in declaration order; an array of zero bytes has no copy
+    for (int i = 0; i < plan.n; i++) {
+      const StagePlan::Array& a = plan.a[i];
+      if (a.out != outputs || !a.bytes) continue;
+      if (outputs) HIPCK(hipMemcpyAsync(host[i], blk + a.off, a.bytes, hipMemcpyDeviceToHost, st));
+      else HIPCK(hipMemcpyAsync(blk + a.off, host[i], a.bytes, hipMemcpyHostToDevice, st));
+    }
+    return BJJ_OK;
+  }
+  // noun: what the out-of-memory message calls the block; round_last: the site allocates its last array rounded up to 256 too
+  int begin(DevBlock<uint8_t>& block, const char* noun, bool round_last = false) {
+    { int rc = grow_block(block, plan.total(round_last), who, noun); if (rc) return rc; }
+    { int rc = set_enter(c, S, st); if (rc) return rc; }
+    blk = block;
+    return copy(false);
+  }
+  int finish() {
+    { int rc = copy(true); if (rc) return rc; }
+    { int rc = set_leave(c, S, st); if (rc) return rc; }
+    HIPCK(hipStreamSynchronize(st));
+    return BJJ_OK;
+  }
+};
+// Counts violated conditions on the device: `words` zeroed 64-bit counters, launch(d_counters) enqueues the checker (and what it has
+// to run behind) on the context's stream, the counters come back in h[] -- or the HIP error does, behind "who: ".
+template <typename Launch>
+static int device_counters(bjj_ctx* c, int words, unsigned long long* h, const char* who, Launch launch) {
+  DevBlock<unsigned long long> d;
+  const size_t bytes = (size_t)words * sizeof(unsigned long long);
+  hipError_t e = d.grow(bytes, NO_WAIT);
+  if (e == hipSuccess) e = hipMemsetAsync(d, 0, bytes, c->stream);
+  if (e == hipSuccess) e = launch(d.p);
+  if (e == hipSuccess) e = hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) return set_err(BJJ_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
+  return BJJ_OK;
+}
 
 // Streams, events and the copy workers; the blocks release themselves when the context is deleted -- here, with its device current
 // and idle (the wiped ones zero themselves first: Block::wipe).
@@ -546,12 +633,7 @@ static void ctx_destroy(bjj_ctx* c) {
     if (S.ev_last) hipEventDestroy(S.ev_last);
   }
   for (StreamMark& k : c->marks) if (k.ev) hipEventDestroy(k.ev);
-  for (bjj_base* b : c->user_bases) delete b;   // tables the caller never freed
-  c->user_bases.clear();
-  for (bjj_signer_set* t : c->user_sets) delete t;   // ... and the signer sets
-  c->user_sets.clear();
-  for (bjj_dlog_table* t : c->user_dlogs) delete t;   // ... and the discrete-logarithm tables
-  c->user_dlogs.clear();
+  c->user_bases.clear(); c->user_sets.clear(); c->user_dlogs.clear();   // tables, signer sets and logarithm tables the caller never freed
   delete c->pool;   // joins the copy workers
   c->pool = nullptr;
   for (hipEvent_t e : c->ev_in) hipEventDestroy(e);
@@ -857,14 +939,10 @@ int bjj_get_info(bjj_ctx* c, bjj_info* out) {
 int bjj_check_table(bjj_ctx* c, uint64_t* n_bad) {
   if (!c || !n_bad) return set_err(BJJ_E_INVALID, "bjj_check_table: NULL argument");
   ENTER_DEVICE(c->device);
-  DevBlock<unsigned long long> d_bad;
-  HIPCK(d_bad.grow(sizeof(unsigned long long), NO_WAIT));
-  hipError_t e = hipMemsetAsync(d_bad, 0, sizeof(unsigned long long), c->stream);
-  if (e == hipSuccess) e = bjjk::check_fixed_table(c->stream, c->cus * 8, c->table, c->bases, c->W, c->nwin, d_bad);
   unsigned long long h = 0;
-  if (e == hipSuccess) e = hipMemcpyAsync(&h, d_bad, sizeof(h), hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess) return set_err(BJJ_E_HIP, std::string("bjj_check_table: ") + hipGetErrorString(e));
+  { int rc = device_counters(c, 1, &h, "bjj_check_table", [&](unsigned long long* d_bad) {
+      return bjjk::check_fixed_table(c->stream, c->cus * 8, c->table, c->bases, c->W, c->nwin, d_bad); });
+    if (rc) return rc; }
   *n_bad = (uint64_t)h;
   return BJJ_OK;
 }
@@ -1369,20 +1447,17 @@ static int ensure_ct_table(bjj_ctx* c) {
   ENTER_DEVICE(c->device);
   const int nwin = fixed_nwin(BJJ_CT_W);
   const size_t bytes = fixed_stride(BJJ_CT_W) * (size_t)nwin * NIELS_WORDS * sizeof(u32);
-  DevBlock<unsigned long long> d_bad;
   unsigned long long bad = 1;
-  hipError_t e = c->ct_table.grow(bytes, NO_WAIT);
-  if (e == hipSuccess) e = c->ct_bases.grow((size_t)nwin * NIELS_WORDS * sizeof(u32), NO_WAIT);
-  if (e == hipSuccess) e = d_bad.grow(sizeof(unsigned long long), NO_WAIT);
-  if (e == hipSuccess) e = hipMemsetAsync(d_bad, 0, sizeof(unsigned long long), c->stream);
-  if (e == hipSuccess) e = bjjk::build_fixed_table(c->stream, c->ct_table, c->ct_bases, BJJ_CT_W, nwin);
-  if (e == hipSuccess) e = bjjk::check_fixed_table(c->stream, 8, c->ct_table, c->ct_bases, BJJ_CT_W, nwin, d_bad);   // the same induction proof as the big table
-  if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess || bad != 0) {   // a table that exists is a table that passed: the next call starts over
+  const int rc = device_counters(c, 1, &bad, "constant-time signer table", [&](unsigned long long* d_bad) {
+    hipError_t e = c->ct_table.grow(bytes, NO_WAIT);
+    if (e == hipSuccess) e = c->ct_bases.grow((size_t)nwin * NIELS_WORDS * sizeof(u32), NO_WAIT);
+    if (e == hipSuccess) e = bjjk::build_fixed_table(c->stream, c->ct_table, c->ct_bases, BJJ_CT_W, nwin);
+    if (e == hipSuccess) e = bjjk::check_fixed_table(c->stream, 8, c->ct_table, c->ct_bases, BJJ_CT_W, nwin, d_bad);   // the same induction proof as the big table
+    return e;
+  });
+  if (rc || bad != 0) {   // a table that exists is a table that passed: the next call starts over
     (void)c->ct_table.release(); (void)c->ct_bases.release();
-    return e != hipSuccess ? set_err(BJJ_E_HIP, std::string("constant-time signer table: ") + hipGetErrorString(e))
-                           : set_err(BJJ_E_HIP, "constant-time signer table failed its self-check");
+    return rc ? rc : set_err(BJJ_E_HIP, "constant-time signer table failed its self-check");
   }
   c->occ_sign_ct = bjjk::occ_sign_ct();
   c->occ_sign_schnorr_ct = bjjk::occ_sign_schnorr_ct();
@@ -1643,12 +1718,6 @@ static int msm_check(bjj_ctx* c, size_t n, int window_bits, const char* who) {
     return set_err(BJJ_E_INVALID, std::string(who) + ": window_bits must be 0 (library's choice) or 4..20");
   return BJJ_OK;
 }
-// the set's MSM block holds at least `bytes`; a block this size may well not fit: the set stays usable, with no MSM block
-static int ensure_msm(ScratchSet* S, size_t bytes, const char* who) {
-  if (S->msm.grow(bytes) == hipSuccess) return BJJ_OK;
-  (void)hipGetLastError();
-  return set_err(BJJ_E_NOMEM, std::string(who) + ": cannot allocate " + std::to_string(bytes >> 20) + " MB of MSM scratch");
-}
 int bjj_msm_dev(bjj_ctx* c, const void* d_pts, const void* d_scalars, size_t n, int window_bits, void* d_out, void* d_first_off_curve,
                 void* stream) {
   { int rc = msm_check(c, n, window_bits, "bjj_msm_dev"); if (rc) return rc; }
@@ -1658,47 +1727,25 @@ int bjj_msm_dev(bjj_ctx* c, const void* d_pts, const void* d_scalars, size_t n, 
   ENTER_DEVICE(c->device);
   ScratchSet* S = pick_set(c, st);
   const bjjk::MsmLayout L = bjjk::msm_layout(n, msm_window(n, window_bits));
-  { int rc = ensure_msm(S, L.bytes, "bjj_msm_dev"); if (rc) return rc; }
+  { int rc = grow_block(S->msm, L.bytes, "bjj_msm_dev", "MSM scratch"); if (rc) return rc; }
   { int rc = set_enter(c, S, st); if (rc) return rc; }
   LAUNCHCK(bjjk::msm(st, L, (const uint8_t*)d_pts, (const uint8_t*)d_scalars, n, S->msm, (uint8_t*)d_out, (unsigned long long*)d_first_off_curve),
            "bjj_msm_dev");
   return set_leave(c, S, st);
 }
-// The synchronous host forms of bjj_msm and bjj_msm_batch.  The inputs are copied once, straight from the caller's arrays (pinned or
-// pageable), into the set's block behind the scratch that L lays out; `results` 64-byte records and as many status words come back
-// the same way.  launch(st, blk, d_pts, d_scalars) enqueues what the form has of its own.
-extern "C++" {
-template <typename Launch>
-static int msm_host_run(bjj_ctx* c, const bjjk::MsmLayout& L, const uint8_t* pts, const uint8_t* scalars, size_t n, size_t results,
-                        uint8_t* out_xy, int64_t* out_first_off_curve, const char* who, Launch launch) {
-  hipStream_t st = c->stream;
-  ENTER_DEVICE(c->device);
-  ScratchSet* S = pick_set(c, st);
-  const size_t o_pts = L.bytes, o_sc = o_pts + up256(n * 64);
-  { int rc = ensure_msm(S, o_sc + up256(n * 32), who); if (rc) return rc; }
-  { int rc = set_enter(c, S, st); if (rc) return rc; }
-  uint8_t* blk = S->msm;
-  if (n) {
-    HIPCK(hipMemcpyAsync(blk + o_pts, pts, n * 64, hipMemcpyHostToDevice, st));
-    HIPCK(hipMemcpyAsync(blk + o_sc, scalars, n * 32, hipMemcpyHostToDevice, st));
-  }
-  { int rc = launch(st, blk, blk + o_pts, blk + o_sc); if (rc) return rc; }
-  HIPCK(hipMemcpyAsync(out_xy, blk + L.o_out, results * 64, hipMemcpyDeviceToHost, st));
-  HIPCK(hipMemcpyAsync(out_first_off_curve, blk + L.o_status, results * 8, hipMemcpyDeviceToHost, st));
-  { int rc = set_leave(c, S, st); if (rc) return rc; }
-  HIPCK(hipStreamSynchronize(st));
-  return BJJ_OK;
-}
-}  // extern "C++"
+// Synchronous (Staged): the inputs behind the scratch that L lays out; the result and the status word come back out of L's own slots.
 int bjj_msm(bjj_ctx* c, const uint8_t* pts, const uint8_t* scalars, size_t n, int window_bits, uint8_t* out_xy, int64_t* out_first_off_curve) {
   { int rc = msm_check(c, n, window_bits, "bjj_msm"); if (rc) return rc; }
   if (!out_xy || !out_first_off_curve || (n && (!pts || !scalars))) return set_err(BJJ_E_INVALID, "bjj_msm: NULL buffer");
   const bjjk::MsmLayout L = bjjk::msm_layout(n, msm_window(n, window_bits));
-  return msm_host_run(c, L, pts, scalars, n, 1, out_xy, out_first_off_curve, "bjj_msm",
-                      [&](hipStream_t st, uint8_t* blk, const uint8_t* d_pts, const uint8_t* d_scalars) -> int {
-    LAUNCHCK(bjjk::msm(st, L, d_pts, d_scalars, n, blk, blk + L.o_out, (unsigned long long*)(blk + L.o_status)), "bjj_msm");
-    return BJJ_OK;
-  });
+  ENTER_DEVICE(c->device);
+  Staged G(c, "bjj_msm", L.bytes);
+  const int i_pts = G.in(pts, n, 64), i_sc = G.in(scalars, n, 32);
+  G.out_at(L.o_out, out_xy, 64); G.out_at(L.o_status, out_first_off_curve, 8);
+  { int rc = G.begin(G.S->msm, "MSM scratch", true); if (rc) return rc; }
+  uint8_t* blk = G.blk;
+  LAUNCHCK(bjjk::msm(G.st, L, G.dev(i_pts), G.dev(i_sc), n, blk, blk + L.o_out, (unsigned long long*)(blk + L.o_status)), "bjj_msm");
+  return G.finish();
 }
 
 // ---- bjj_msm_batch: m sums over CSR segments in one launch chain (k_msm_batch.hip, include/bjj_hip_msm_batch.h) -------------------
@@ -1748,7 +1795,7 @@ int bjj_msm_batch_dev(bjj_ctx* c, const void* d_pts, const void* d_scalars, size
   ENTER_DEVICE(c->device);
   ScratchSet* S = pick_set(c, st);
   const bjjk::MsmLayout L = bjjk::msm_batch_layout(n, m, w);
-  { int rc = ensure_msm(S, L.bytes, "bjj_msm_batch_dev"); if (rc) return rc; }
+  { int rc = grow_block(S->msm, L.bytes, "bjj_msm_batch_dev", "MSM scratch"); if (rc) return rc; }
   { int rc = set_enter(c, S, st); if (rc) return rc; }
   LAUNCHCK(bjjk::msm_batch(st, L, (const uint8_t*)d_pts, (const uint8_t*)d_scalars, n, (const uint64_t*)d_offsets, m, S->msm, (uint8_t*)d_out,
                            (unsigned long long*)d_first_off_curve),
@@ -1767,14 +1814,16 @@ int bjj_msm_batch(bjj_ctx* c, const uint8_t* pts, const uint8_t* scalars, size_t
     if (offsets[s] > offsets[s + 1]) return set_err(BJJ_E_INVALID, "bjj_msm_batch: offsets decrease at segment " + std::to_string(s));
   if (offsets[m] != n) return set_err(BJJ_E_INVALID, "bjj_msm_batch: offsets[m] must equal n");
   const bjjk::MsmLayout L = bjjk::msm_batch_layout(n, m, w);
-  return msm_host_run(c, L, pts, scalars, n, m, out_xy, out_first_off_curve, "bjj_msm_batch",
-                      [&](hipStream_t st, uint8_t* blk, const uint8_t* d_pts, const uint8_t* d_scalars) -> int {
-    HIPCK(hipMemcpyAsync(blk + L.o_offsets, offsets, (m + 1) * 8, hipMemcpyHostToDevice, st));
-    LAUNCHCK(bjjk::msm_batch(st, L, d_pts, d_scalars, n, (const uint64_t*)(blk + L.o_offsets), m, blk, blk + L.o_out,
-                             (unsigned long long*)(blk + L.o_status)),
-             "bjj_msm_batch");
-    return BJJ_OK;
-  });
+  ENTER_DEVICE(c->device);
+  Staged G(c, "bjj_msm_batch", L.bytes);
+  const int i_pts = G.in(pts, n, 64), i_sc = G.in(scalars, n, 32), i_off = G.in_at(L.o_offsets, offsets, (m + 1) * 8);
+  G.out_at(L.o_out, out_xy, m * 64); G.out_at(L.o_status, out_first_off_curve, m * 8);
+  { int rc = G.begin(G.S->msm, "MSM scratch", true); if (rc) return rc; }
+  uint8_t* blk = G.blk;
+  LAUNCHCK(bjjk::msm_batch(G.st, L, G.dev(i_pts), G.dev(i_sc), n, (const uint64_t*)G.dev(i_off), m, blk, blk + L.o_out,
+                           (unsigned long long*)(blk + L.o_status)),
+           "bjj_msm_batch");
+  return G.finish();
 }
 
 // ---- fixed-base tables for caller-chosen points (k_bases.hip, bases.hpp, include/bjj_hip_bases.h) --------------------------------
@@ -1788,19 +1837,9 @@ static bool point_words_on_curve(const u32 xy[16]) {
   const Fr rhs = fr_add(fr_one(), fr_mul(fr_to_mont_words(d), fr_mul(x2, y2)));
   return fr_eq(lhs, rhs);
 }
-static bool base_of_ctx(const bjj_ctx* c, const bjj_base* b) {
-  for (const bjj_base* k : c->user_bases) if (k == b) return true;
-  return false;
-}
 static int base_run_check(bjj_ctx* c, const bjj_base* b, unsigned long long* bad, const char* who) {
-  DevBlock<unsigned long long> d_bad;
-  hipError_t e = d_bad.grow(sizeof(unsigned long long), NO_WAIT);
-  if (e == hipSuccess) e = hipMemsetAsync(d_bad, 0, sizeof(unsigned long long), c->stream);
-  if (e == hipSuccess) e = bjjk::check_base_table(c->stream, c->cus * 8, b->table, b->bases, b->W, b->nwin, b->xy, d_bad);
-  if (e == hipSuccess) e = hipMemcpyAsync(bad, d_bad, sizeof(*bad), hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess) return set_err(BJJ_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
-  return BJJ_OK;
+  return device_counters(c, 1, bad, who, [&](unsigned long long* d_bad) {
+    return bjjk::check_base_table(c->stream, c->cus * 8, b->table, b->bases, b->W, b->nwin, b->xy, d_bad); });
 }
 int bjj_base_create(bjj_ctx* c, const uint8_t* point_xy, int window_bits, bjj_base** out) {
   CHECK_CTX(c, "bjj_base_create");
@@ -1830,19 +1869,17 @@ int bjj_base_create(bjj_ctx* c, const uint8_t* point_xy, int window_bits, bjj_ba
   unsigned long long bad = 1;   // a handle that exists is a table that passed (the rule of ensure_ct_table)
   { int rc = base_run_check(c, b, &bad, "bjj_base_create"); if (rc) { delete b; return rc; } }
   if (bad != 0) { delete b; return set_err(BJJ_E_HIP, "bjj_base_create: the table failed its self-check (" + std::to_string(bad) + " conditions)"); }
-  try { c->user_bases.push_back(b); } catch (...) { delete b; return set_err(BJJ_E_NOMEM, "bjj_base_create: out of host memory"); }
+  try { c->user_bases.add(b); } catch (...) { delete b; return set_err(BJJ_E_NOMEM, "bjj_base_create: out of host memory"); }
   *out = b;
   return BJJ_OK;
 }
 int bjj_base_free(bjj_ctx* c, bjj_base* b) {
   CHECK_CTX(c, "bjj_base_free");
   if (!b) return BJJ_OK;
-  if (!base_of_ctx(c, b)) return set_err(BJJ_E_INVALID, "bjj_base_free: not a base of this context");
+  if (!c->user_bases.owns(b)) return set_err(BJJ_E_INVALID, "bjj_base_free: not a base of this context");
   ENTER_DEVICE(c->device);
   { int rc = ctx_wait_enqueued(c); if (rc) return rc; }   // launches that gather from the table
-  for (size_t i = 0; i < c->user_bases.size(); i++)
-    if (c->user_bases[i] == b) { c->user_bases.erase(c->user_bases.begin() + (long)i); break; }
-  delete b;
+  c->user_bases.drop(b);
   return BJJ_OK;
 }
 int bjj_base_info(const bjj_base* b, int* window_bits, int* n_windows, uint64_t* table_bytes) {
@@ -1855,7 +1892,7 @@ int bjj_base_info(const bjj_base* b, int* window_bits, int* n_windows, uint64_t*
 int bjj_base_check(bjj_ctx* c, const bjj_base* b, uint64_t* n_bad) {
   CHECK_CTX(c, "bjj_base_check");
   if (!b || !n_bad) return set_err(BJJ_E_INVALID, "bjj_base_check: NULL argument");
-  if (!base_of_ctx(c, b)) return set_err(BJJ_E_INVALID, "bjj_base_check: not a base of this context");
+  if (!c->user_bases.owns(b)) return set_err(BJJ_E_INVALID, "bjj_base_check: not a base of this context");
   ENTER_DEVICE(c->device);
   unsigned long long bad = 0;
   { int rc = base_run_check(c, b, &bad, "bjj_base_check"); if (rc) return rc; }
@@ -1873,7 +1910,7 @@ static int mul_bases_check(bjj_ctx* c, const bjj_base* const* bases, int t, cons
   A->t = t;
   for (int j = 0; j < t; j++) {
     const bjj_base* b = bases[j];
-    if (b && !base_of_ctx(c, b)) return set_err(BJJ_E_INVALID, std::string(who) + ": bases[" + std::to_string(j) + "] is not a base of this context");
+    if (b && !c->user_bases.owns(b)) return set_err(BJJ_E_INVALID, std::string(who) + ": bases[" + std::to_string(j) + "] is not a base of this context");
     if (n && !scalars[j]) return set_err(BJJ_E_INVALID, std::string(who) + ": scalars[" + std::to_string(j) + "] is NULL");
     A->b[j].table = b ? b->table.p : c->table.p;
     A->b[j].W = b ? b->W : c->W;
@@ -1893,32 +1930,21 @@ int bjj_mul_bases_dev(bjj_ctx* c, const bjj_base* const* bases, int t, const voi
   LAUNCHCK(bjjk::mul_bases(st, c->cus, c->lanes_bases, A, n, (uint8_t*)d_out, S->scratch), "bjj_mul_bases_dev");
   SET_LEAVE(c);
 }
-// Synchronous: the t scalar arrays go to the set's block with one copy each (pinned or pageable), one launch, one copy out.
+// Synchronous (Staged): the t scalar arrays, then the results
 int bjj_mul_bases(bjj_ctx* c, const bjj_base* const* bases, int t, const uint8_t* const* scalars, size_t n, uint8_t* out_xy) {
   BasesArgs A;
   { int rc = mul_bases_check(c, bases, t, (const void* const*)scalars, n, "bjj_mul_bases", &A); if (rc) return rc; }
   if (n == 0) return BJJ_OK;
   if (!out_xy) return set_err(BJJ_E_INVALID, "bjj_mul_bases: out_xy is NULL");
-  hipStream_t st = c->stream;
   ENTER_DEVICE(c->device);
-  ScratchSet* S = pick_set(c, st);
-  { int rc = ensure_scratch(c, S, n); if (rc) return rc; }
-  const size_t sc_bytes = up256(n * 32), o_out = (size_t)t * sc_bytes;
-  if (S->bases_io.grow(o_out + n * 64) != hipSuccess) {
-    (void)hipGetLastError();
-    return set_err(BJJ_E_NOMEM, "bjj_mul_bases: cannot allocate " + std::to_string((o_out + n * 64) >> 20) + " MB of device staging");
-  }
-  { int rc = set_enter(c, S, st); if (rc) return rc; }
-  uint8_t* blk = S->bases_io;
-  for (int j = 0; j < t; j++) {
-    HIPCK(hipMemcpyAsync(blk + (size_t)j * sc_bytes, scalars[j], n * 32, hipMemcpyHostToDevice, st));
-    A.b[j].scalars = blk + (size_t)j * sc_bytes;
-  }
-  LAUNCHCK(bjjk::mul_bases(st, c->cus, c->lanes_bases, A, n, blk + o_out, S->scratch), "bjj_mul_bases");
-  HIPCK(hipMemcpyAsync(out_xy, blk + o_out, n * 64, hipMemcpyDeviceToHost, st));
-  { int rc = set_leave(c, S, st); if (rc) return rc; }
-  HIPCK(hipStreamSynchronize(st));
-  return BJJ_OK;
+  Staged G(c, "bjj_mul_bases");
+  { int rc = ensure_scratch(c, G.S, n); if (rc) return rc; }
+  for (int j = 0; j < t; j++) G.in(scalars[j], n, 32);   // array j of the plan
+  const int i_out = G.out(out_xy, n, 64);
+  { int rc = G.begin(G.S->bases_io, "device staging"); if (rc) return rc; }
+  for (int j = 0; j < t; j++) A.b[j].scalars = G.dev(j);
+  LAUNCHCK(bjjk::mul_bases(G.st, c->cus, c->lanes_bases, A, n, G.dev(i_out), G.S->scratch), "bjj_mul_bases");
+  return G.finish();
 }
 
 // ---- verification against one signer's table (include/bjj_hip_signer.h) ------------------------------------------------------
@@ -1926,13 +1952,17 @@ int bjj_mul_bases(bjj_ctx* c, const bjj_base* const* bases, int t, const uint8_t
 static int verify_signer_check(bjj_ctx* c, const bjj_base* signer, size_t n, const char* who, SignerArgs* A) {
   if (!c) return set_err(BJJ_E_INVALID, std::string(who) + ": ctx is NULL");
   if (!signer) return set_err(BJJ_E_INVALID, std::string(who) + ": signer is NULL");
-  if (!base_of_ctx(c, signer)) return set_err(BJJ_E_INVALID, std::string(who) + ": signer is not a base of this context");
+  if (!c->user_bases.owns(signer)) return set_err(BJJ_E_INVALID, std::string(who) + ": signer is not a base of this context");
   CHECK_N(n);
   memset(A, 0, sizeof(*A));
   A->T.table = signer->table.p; A->T.W = signer->W; A->T.nwin = signer->nwin; A->T.mod_l = 0;
   A->L.table = c->table.p; A->L.W = c->W; A->L.nwin = c->nwin; A->L.mod_l = 1;
   A->pk = signer_point(signer->xy);
   return BJJ_OK;
+}
+static hipError_t verify_signer_enqueue(bjj_ctx* c, hipStream_t st, bool schnorr, const SignerArgs& A, const uint8_t* r, const uint8_t* s,
+                                        const uint8_t* msg, size_t n, uint8_t* ok) {
+  return bjjk::verify_signer(st, c->cus, c->lanes_signer, schnorr, A, r, s, msg, n, ok);
 }
 // No scratch set: the kernel keeps everything in registers and LDS, so calls on different streams share nothing.
 static int verify_signer_dev(bjj_ctx* c, bool schnorr, const bjj_base* signer, const void* d_r, const void* d_s, const void* d_msg, size_t n,
@@ -1944,35 +1974,22 @@ static int verify_signer_dev(bjj_ctx* c, bool schnorr, const bjj_base* signer, c
     return set_err(BJJ_E_INVALID, std::string(who) + ": NULL or not 16-byte aligned device pointer");
   if (!d_ok) return set_err(BJJ_E_INVALID, std::string(who) + ": d_ok is NULL");
   DEV_ENTER(c, stream);
-  LAUNCHCK_S(bjjk::verify_signer(st, c->cus, c->lanes_signer, schnorr, A, (const uint8_t*)d_r, (const uint8_t*)d_s, (const uint8_t*)d_msg, n,
-                                 (uint8_t*)d_ok), who);
+  LAUNCHCK_S(verify_signer_enqueue(c, st, schnorr, A, (const uint8_t*)d_r, (const uint8_t*)d_s, (const uint8_t*)d_msg, n, (uint8_t*)d_ok), who);
   DEV_LEAVE(c);
 }
-// Synchronous: the three arrays go to the set's block with one copy each (pinned or pageable), one launch, one copy out.
+// Synchronous (Staged): R, s, msg, then the verdicts
 static int verify_signer_host(bjj_ctx* c, bool schnorr, const bjj_base* signer, const uint8_t* r, const uint8_t* s, const uint8_t* msg, size_t n,
                               uint8_t* ok, const char* who) {
   SignerArgs A;
   { int rc = verify_signer_check(c, signer, n, who, &A); if (rc) return rc; }
   if (n == 0) return BJJ_OK;
   if (!r || !s || !msg || !ok) return set_err(BJJ_E_INVALID, std::string(who) + ": NULL buffer");
-  hipStream_t st = c->stream;
   ENTER_DEVICE(c->device);
-  ScratchSet* S = pick_set(c, st);
-  const size_t o_s = up256(n * 64), o_msg = o_s + up256(n * 32), o_ok = o_msg + up256(n * 32);
-  if (S->bases_io.grow(o_ok + n) != hipSuccess) {
-    (void)hipGetLastError();
-    return set_err(BJJ_E_NOMEM, std::string(who) + ": cannot allocate " + std::to_string((o_ok + n) >> 20) + " MB of device staging");
-  }
-  { int rc = set_enter(c, S, st); if (rc) return rc; }
-  uint8_t* blk = S->bases_io;
-  HIPCK(hipMemcpyAsync(blk, r, n * 64, hipMemcpyHostToDevice, st));
-  HIPCK(hipMemcpyAsync(blk + o_s, s, n * 32, hipMemcpyHostToDevice, st));
-  HIPCK(hipMemcpyAsync(blk + o_msg, msg, n * 32, hipMemcpyHostToDevice, st));
-  LAUNCHCK_S(bjjk::verify_signer(st, c->cus, c->lanes_signer, schnorr, A, blk, blk + o_s, blk + o_msg, n, blk + o_ok), who);
-  HIPCK(hipMemcpyAsync(ok, blk + o_ok, n, hipMemcpyDeviceToHost, st));
-  { int rc = set_leave(c, S, st); if (rc) return rc; }
-  HIPCK(hipStreamSynchronize(st));
-  return BJJ_OK;
+  Staged G(c, who);
+  const int i_r = G.in(r, n, 64), i_s = G.in(s, n, 32), i_msg = G.in(msg, n, 32), i_ok = G.out(ok, n, 1);
+  { int rc = G.begin(G.S->bases_io, "device staging"); if (rc) return rc; }
+  LAUNCHCK_S(verify_signer_enqueue(c, G.st, schnorr, A, G.dev(i_r), G.dev(i_s), G.dev(i_msg), n, G.dev(i_ok)), who);
+  return G.finish();
 }
 int bjj_eddsa_verify_signer(bjj_ctx* c, const bjj_base* signer, const uint8_t* r_xy, const uint8_t* s, const uint8_t* msg, size_t n, uint8_t* ok) {
   return verify_signer_host(c, false, signer, r_xy, s, msg, n, ok, "bjj_eddsa_verify_signer");
@@ -1993,19 +2010,9 @@ int bjj_schnorr_verify_signer_dev(bjj_ctx* c, const bjj_base* signer, const void
 #define BJJ_SET_DEFAULT_WINDOW_BITS 8
 #define BJJ_SET_MAX_WINDOW_BITS 16
 static_assert(BJJ_VERIFY_BAD_SIGNER == BJJ_SET_BAD_SIGNER, "include/bjj_hip_signer_set.h and signer_set.hpp disagree");
-static bool set_of_ctx(const bjj_ctx* c, const bjj_signer_set* t) {
-  for (const bjj_signer_set* k : c->user_sets) if (k == t) return true;
-  return false;
-}
 static int set_run_check(bjj_ctx* c, const bjj_signer_set* t, unsigned long long* bad, const char* who) {
-  DevBlock<unsigned long long> d_bad;
-  hipError_t e = d_bad.grow(sizeof(unsigned long long), NO_WAIT);
-  if (e == hipSuccess) e = hipMemsetAsync(d_bad, 0, sizeof(unsigned long long), c->stream);
-  if (e == hipSuccess) e = bjjk::check_signer_set(c->stream, c->cus * 8, t->table, t->bases, t->keys, t->k, t->W, t->nwin, d_bad);
-  if (e == hipSuccess) e = hipMemcpyAsync(bad, d_bad, sizeof(*bad), hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess) return set_err(BJJ_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
-  return BJJ_OK;
+  return device_counters(c, 1, bad, who, [&](unsigned long long* d_bad) {
+    return bjjk::check_signer_set(c->stream, c->cus * 8, t->table, t->bases, t->keys, t->k, t->W, t->nwin, d_bad); });
 }
 int bjj_signer_set_create(bjj_ctx* c, const uint8_t* pks_xy, size_t k, int window_bits, bjj_signer_set** out, int64_t* out_first_off_curve) {
   CHECK_CTX(c, "bjj_signer_set_create");
@@ -2047,7 +2054,7 @@ int bjj_signer_set_create(bjj_ctx* c, const uint8_t* pks_xy, size_t k, int windo
   unsigned long long bad = 1;   // a handle that exists is a set that passed (the rule of bjj_base_create)
   { int rc = set_run_check(c, t, &bad, "bjj_signer_set_create"); if (rc) { delete t; return rc; } }
   if (bad != 0) { delete t; return set_err(BJJ_E_HIP, "bjj_signer_set_create: the tables failed their self-check (" + std::to_string(bad) + " conditions)"); }
-  try { c->user_sets.push_back(t); } catch (...) { delete t; return set_err(BJJ_E_NOMEM, "bjj_signer_set_create: out of host memory"); }
+  try { c->user_sets.add(t); } catch (...) { delete t; return set_err(BJJ_E_NOMEM, "bjj_signer_set_create: out of host memory"); }
   if (out_first_off_curve) *out_first_off_curve = -1;
   *out = t;
   return BJJ_OK;
@@ -2055,12 +2062,10 @@ int bjj_signer_set_create(bjj_ctx* c, const uint8_t* pks_xy, size_t k, int windo
 int bjj_signer_set_free(bjj_ctx* c, bjj_signer_set* t) {
   CHECK_CTX(c, "bjj_signer_set_free");
   if (!t) return BJJ_OK;
-  if (!set_of_ctx(c, t)) return set_err(BJJ_E_INVALID, "bjj_signer_set_free: not a signer set of this context");
+  if (!c->user_sets.owns(t)) return set_err(BJJ_E_INVALID, "bjj_signer_set_free: not a signer set of this context");
   ENTER_DEVICE(c->device);
   { int rc = ctx_wait_enqueued(c); if (rc) return rc; }   // launches that gather from the tables
-  for (size_t i = 0; i < c->user_sets.size(); i++)
-    if (c->user_sets[i] == t) { c->user_sets.erase(c->user_sets.begin() + (long)i); break; }
-  delete t;
+  c->user_sets.drop(t);
   return BJJ_OK;
 }
 int bjj_signer_set_info(const bjj_signer_set* t, uint64_t* n_signers, int* window_bits, int* n_windows, uint64_t* table_bytes) {
@@ -2074,7 +2079,7 @@ int bjj_signer_set_info(const bjj_signer_set* t, uint64_t* n_signers, int* windo
 int bjj_signer_set_check(bjj_ctx* c, const bjj_signer_set* t, uint64_t* n_bad) {
   CHECK_CTX(c, "bjj_signer_set_check");
   if (!t || !n_bad) return set_err(BJJ_E_INVALID, "bjj_signer_set_check: NULL argument");
-  if (!set_of_ctx(c, t)) return set_err(BJJ_E_INVALID, "bjj_signer_set_check: not a signer set of this context");
+  if (!c->user_sets.owns(t)) return set_err(BJJ_E_INVALID, "bjj_signer_set_check: not a signer set of this context");
   ENTER_DEVICE(c->device);
   unsigned long long bad = 0;
   { int rc = set_run_check(c, t, &bad, "bjj_signer_set_check"); if (rc) return rc; }
@@ -2085,13 +2090,17 @@ int bjj_signer_set_check(bjj_ctx* c, const bjj_signer_set* t, uint64_t* n_bad) {
 static int verify_set_check(bjj_ctx* c, const bjj_signer_set* t, size_t n, const char* who, SetArgs* A) {
   if (!c) return set_err(BJJ_E_INVALID, std::string(who) + ": ctx is NULL");
   if (!t) return set_err(BJJ_E_INVALID, std::string(who) + ": set is NULL");
-  if (!set_of_ctx(c, t)) return set_err(BJJ_E_INVALID, std::string(who) + ": set is not a signer set of this context");
+  if (!c->user_sets.owns(t)) return set_err(BJJ_E_INVALID, std::string(who) + ": set is not a signer set of this context");
   CHECK_N(n);
   memset(A, 0, sizeof(*A));
   A->T.table = t->table.p; A->T.W = t->W; A->T.nwin = t->nwin; A->T.mod_l = 0;
   A->L.table = c->table.p; A->L.W = c->W; A->L.nwin = c->nwin; A->L.mod_l = 1;
   A->keys = t->keys.p; A->k = (u32)t->k; A->eps = (u32)set_entries_per_signer(t->W);
   return BJJ_OK;
+}
+static hipError_t verify_set_enqueue(bjj_ctx* c, hipStream_t st, bool schnorr, const SetArgs& A, const uint32_t* idx, const uint8_t* r,
+                                     const uint8_t* s, const uint8_t* msg, size_t n, uint8_t* ok) {
+  return bjjk::verify_set(st, c->cus, c->lanes_set, schnorr, A, idx, r, s, msg, n, ok);
 }
 // No scratch set: the kernel keeps everything in registers and LDS, so calls on different streams share nothing.
 static int verify_set_dev(bjj_ctx* c, bool schnorr, const bjj_signer_set* t, const void* d_idx, const void* d_r, const void* d_s,
@@ -2103,36 +2112,23 @@ static int verify_set_dev(bjj_ctx* c, bool schnorr, const bjj_signer_set* t, con
     return set_err(BJJ_E_INVALID, std::string(who) + ": NULL or not 16-byte aligned device pointer");
   if (!d_ok) return set_err(BJJ_E_INVALID, std::string(who) + ": d_ok is NULL");
   DEV_ENTER(c, stream);
-  LAUNCHCK_S(bjjk::verify_set(st, c->cus, c->lanes_set, schnorr, A, (const uint32_t*)d_idx, (const uint8_t*)d_r, (const uint8_t*)d_s,
-                              (const uint8_t*)d_msg, n, (uint8_t*)d_ok), who);
+  LAUNCHCK_S(verify_set_enqueue(c, st, schnorr, A, (const uint32_t*)d_idx, (const uint8_t*)d_r, (const uint8_t*)d_s, (const uint8_t*)d_msg, n,
+                                (uint8_t*)d_ok), who);
   DEV_LEAVE(c);
 }
-// Synchronous: the four arrays go to the set's block with one copy each (pinned or pageable), one launch, one copy out.
+// Synchronous (Staged): R, s, msg and the indices (behind the records, as the block always held them), then the verdicts
 static int verify_set_host(bjj_ctx* c, bool schnorr, const bjj_signer_set* t, const uint32_t* idx, const uint8_t* r, const uint8_t* s,
                            const uint8_t* msg, size_t n, uint8_t* ok, const char* who) {
   SetArgs A;
   { int rc = verify_set_check(c, t, n, who, &A); if (rc) return rc; }
   if (n == 0) return BJJ_OK;
   if (!idx || !r || !s || !msg || !ok) return set_err(BJJ_E_INVALID, std::string(who) + ": NULL buffer");
-  hipStream_t st = c->stream;
   ENTER_DEVICE(c->device);
-  ScratchSet* S = pick_set(c, st);
-  const size_t o_s = up256(n * 64), o_msg = o_s + up256(n * 32), o_idx = o_msg + up256(n * 32), o_ok = o_idx + up256(n * 4);
-  if (S->bases_io.grow(o_ok + n) != hipSuccess) {
-    (void)hipGetLastError();
-    return set_err(BJJ_E_NOMEM, std::string(who) + ": cannot allocate " + std::to_string((o_ok + n) >> 20) + " MB of device staging");
-  }
-  { int rc = set_enter(c, S, st); if (rc) return rc; }
-  uint8_t* blk = S->bases_io;
-  HIPCK(hipMemcpyAsync(blk, r, n * 64, hipMemcpyHostToDevice, st));
-  HIPCK(hipMemcpyAsync(blk + o_s, s, n * 32, hipMemcpyHostToDevice, st));
-  HIPCK(hipMemcpyAsync(blk + o_msg, msg, n * 32, hipMemcpyHostToDevice, st));
-  HIPCK(hipMemcpyAsync(blk + o_idx, idx, n * 4, hipMemcpyHostToDevice, st));
-  LAUNCHCK_S(bjjk::verify_set(st, c->cus, c->lanes_set, schnorr, A, (const uint32_t*)(blk + o_idx), blk, blk + o_s, blk + o_msg, n, blk + o_ok), who);
-  HIPCK(hipMemcpyAsync(ok, blk + o_ok, n, hipMemcpyDeviceToHost, st));
-  { int rc = set_leave(c, S, st); if (rc) return rc; }
-  HIPCK(hipStreamSynchronize(st));
-  return BJJ_OK;
+  Staged G(c, who);
+  const int i_r = G.in(r, n, 64), i_s = G.in(s, n, 32), i_msg = G.in(msg, n, 32), i_idx = G.in(idx, n, 4), i_ok = G.out(ok, n, 1);
+  { int rc = G.begin(G.S->bases_io, "device staging"); if (rc) return rc; }
+  LAUNCHCK_S(verify_set_enqueue(c, G.st, schnorr, A, (const uint32_t*)G.dev(i_idx), G.dev(i_r), G.dev(i_s), G.dev(i_msg), n, G.dev(i_ok)), who);
+  return G.finish();
 }
 int bjj_eddsa_verify_set(bjj_ctx* c, const bjj_signer_set* set, const uint32_t* signer_idx, const uint8_t* r_xy, const uint8_t* s,
                          const uint8_t* msg, size_t n, uint8_t* ok) {
