@@ -22,6 +22,11 @@
 #define BJJ_QUAD_ITEMS (BJJ_QUAD_BLOCK / 4)
 #define QTBL_ENTRY_WORDS (NL * 4)                  // one table entry of one item: 9 limbs x 4 lanes
 #define QTBL_ITEM_WORDS (9 * QTBL_ENTRY_WORDS)     // entries 0 .. 8
+// the launchers' grid: `per` items per workgroup, never empty
+static inline dim3 grid_for(size_t n, size_t per) {
+  const size_t grid = (n + per - 1) / per;
+  return dim3((unsigned)(grid ? grid : 1));
+}
 
 // the value lane (4k + SRC) holds, on every lane of quad k
 template <int SRC>
@@ -80,10 +85,76 @@ __device__ __forceinline__ Fr qtbl_load(const u32* t, int d, int q) {
   for (int i = 0; i < NL; i++) n.v[i] = t[k * QTBL_ENTRY_WORDS + i * 4 + qq];
   return fr_select(neg && q == 3, fr_sub_lazy(fr_zero(), n), n);
 }
+// P given by its affine coordinates on the reference curve, on the a' = -1 curve (ext_from_ref_affine): one coordinate per lane
+__device__ __forceinline__ Fr quad_from_ref_affine(int q, const Fr& x, const Fr& y) {
+  const Fr X = fr_mul(x, c_K.F);
+  return fr_select(q == 0, X, fr_select(q == 1, y, fr_select(q == 2, fr_one(), fr_mul(X, y))));
+}
+// the item's table 0 .. 8 P for P = c (any Z): vb_build_table.  The caller's __syncthreads() orders the stores before the loads of the quad's other lanes
+__device__ __forceinline__ void qtbl_build(int q, u32* tbl, const Fr& c) {
+  const PNiels id = pniels_identity();
+  qtbl_store(tbl, 0, q, fr_select(q == 0, id.ymx, fr_select(q == 1, id.ypx, fr_select(q == 2, id.z2, id.t2d))));
+  const Fr p1 = quad_entry(q, c);
+  qtbl_store(tbl, 1, q, p1);
+  Fr cur = c;
+#pragma unroll 1
+  for (int k = 2; k <= 8; k++) {
+    cur = quad_add(q, cur, p1);
+    qtbl_store(tbl, k, q, quad_entry(q, cur));
+  }
+}
+// signed 4-bit windows (vb_mul_windowed): the words of sc + 0x88..8, for a scalar in words (< 2^254); recode_signed4(Fr) of bjj_device.hpp is the same from limbs
+__device__ __forceinline__ void recode_signed4(const u32 sc[8], u32 t[8]) {
+  u64 cy = 0;
+#pragma unroll
+  for (int k = 0; k < 8; k++) { cy += (u64)sc[k] + 0x88888888u; t[k] = (u32)cy; cy >>= 32; }
+}
+// digit j (-8 .. 7) of a recoded scalar
+__device__ __forceinline__ int signed4_digit(const u32 t[8], int j) { return (int)((t[j >> 3] >> ((j & 7) * 4)) & 15u) - 8; }
+// top window: the table entry e itself as a point (pniels_to_ext).  WITH_T where an addition follows at once: 2T = (2D'T) / D' on lane 3; doublings do not read T
+template <bool WITH_T>
+__device__ __forceinline__ Fr quad_lift(int q, const Fr& e) {
+  const Fr ymx = quad_bcast<0>(e), ypx = quad_bcast<1>(e);
+  Fr t = fr_zero();
+  if constexpr (WITH_T) t = fr_mul(e, c_K.DPINV);
+  return fr_select(q == 0, fr_reduce_weak(fr_sub8(ypx, ymx)), fr_select(q == 1, fr_reduce_weak(fr_add(ypx, ymx)), fr_select(q == 2, fr_reduce_weak(e), t)));
+}
+// windows `from` .. 0 of the recoded scalar t over the table of 0 .. 8 P, most significant first: acc = 16 acc + digit P per window
+__device__ __forceinline__ Fr quad_walk(const u32* tbl, const u32 t[8], int from, int q, Fr acc) {
+#pragma unroll 1
+  for (int j = from; j >= 0; j--) {
+    const Fr e = qtbl_load(tbl, signed4_digit(t, j), q);   // issued ahead of the doublings
+#pragma unroll 1
+    for (int k = 0; k < 4; k++) acc = quad_dbl(q, acc);
+    acc = quad_add(q, acc, e);
+  }
+  return acc;
+}
+// ... of two scalars over their tables in one loop (joint_mul_windowed): the doublings are shared
+__device__ __forceinline__ Fr quad_walk_joint(const u32* tbl1, const u32* tbl2, const u32 tu[8], const u32 tv[8], int from, int q, Fr acc) {
+#pragma unroll 1
+  for (int j = from; j >= 0; j--) {
+    const Fr e1 = qtbl_load(tbl1, signed4_digit(tu, j), q), e2 = qtbl_load(tbl2, signed4_digit(tv, j), q);
+#pragma unroll 1
+    for (int k = 0; k < 4; k++) acc = quad_dbl(q, acc);
+    acc = quad_add(q, acc, e1);
+    acc = quad_add(q, acc, e2);
+  }
+  return acc;
+}
+// affine, back on the reference curve, canonical (epilogue_finish): lane 0: x = X / (Z F), lane 1: y = Y / Z (lanes 2, 3: nobody's value).  zinv = fr_inv(quad_bcast<2>(c)),
+// the item's OWN inversion, comes from the kernel: fr_inv is a real call, and its argument and result are stack slots of whoever makes it -- made in here they
+// would lie in front of the kernel's word arrays, and the frame (bjj_k_mul_var_base_quad: 112 bytes) would grow by the padding between them
+__device__ __forceinline__ Fr quad_affine(int q, const Fr& c, const Fr& zinv) {
+  constexpr u32 R1[NL] = {BJJ_N0, BJJ_N1, BJJ_N2, BJJ_N3, BJJ_N4, BJJ_N5, BJJ_N6, BJJ_N7, BJJ_N8};
+  const Fr zi = fr_mul(zinv, fr_one_plain());                        // plain 1/Z
+  const Fr m = fr_select(q == 0, fr_mul(zi, c_K.FINV), zi);
+  return fr_cond_sub_kr(fr_mul(c, m), R1);
+}
 
+// n P: the point's on-curve test and the scalar mod 8l here; then quad_from_ref_affine, qtbl_build, recode_signed4, quad_lift of window 63, quad_walk over 62 .. 0, quad_affine
 __global__ void __launch_bounds__(BJJ_QUAD_BLOCK) bjj_k_mul_var_base_quad(const uint8_t* __restrict__ pts, const uint8_t* __restrict__ scalars,
                                                                       size_t n, uint8_t* __restrict__ out, u32* __restrict__ slow) {
-  constexpr u32 R1[NL] = {BJJ_N0, BJJ_N1, BJJ_N2, BJJ_N3, BJJ_N4, BJJ_N5, BJJ_N6, BJJ_N7, BJJ_N8};
   __shared__ u32 tbl_all[BJJ_QUAD_ITEMS * QTBL_ITEM_WORDS];   // 20.7 KB
   const int lane = threadIdx.x, q = lane & 3;
   u32* tbl = tbl_all + (lane >> 2) * QTBL_ITEM_WORDS;
@@ -99,49 +170,13 @@ __global__ void __launch_bounds__(BJJ_QUAD_BLOCK) bjj_k_mul_var_base_quad(const 
   y = fr_select(on, y, fr_one());
   load_w8(scalars + i * 32, sc);
   scalar_mod_order(sc, red, c_K);
-  // P on the a' = -1 curve (ext_from_ref_affine), one coordinate per lane
-  const Fr X = fr_mul(x, c_K.F);
-  const Fr T = fr_mul(X, y);
-  Fr c = fr_select(q == 0, X, fr_select(q == 1, y, fr_select(q == 2, fr_one(), T)));
-  // table 0 .. 8 P (vb_build_table)
-  {
-    const PNiels id = pniels_identity();
-    qtbl_store(tbl, 0, q, fr_select(q == 0, id.ymx, fr_select(q == 1, id.ypx, fr_select(q == 2, id.z2, id.t2d))));
-    const Fr p1 = quad_entry(q, c);
-    qtbl_store(tbl, 1, q, p1);
-    Fr cur = c;
-#pragma unroll 1
-    for (int k = 2; k <= 8; k++) {
-      cur = quad_add(q, cur, p1);
-      qtbl_store(tbl, k, q, quad_entry(q, cur));
-    }
-  }
+  qtbl_build(q, tbl, quad_from_ref_affine(q, x, y));
   __syncthreads();                               // one wave: orders the table stores before the loads of the quad's other lanes
-  // signed 4-bit windows, most significant first (vb_mul_windowed)
   u32 t[8];
-  {
-    u64 cy = 0;
-#pragma unroll
-    for (int k = 0; k < 8; k++) { cy += (u64)red[k] + 0x88888888u; t[k] = (u32)cy; cy >>= 32; }
-  }
-  {  // top window: the entry itself as a point (pniels_to_ext; T is not needed: doublings follow)
-    const int d = (int)((t[7] >> 28) & 15u) - 8;
-    const Fr e = qtbl_load(tbl, d, q);
-    const Fr ymx = quad_bcast<0>(e), ypx = quad_bcast<1>(e);
-    c = fr_select(q == 0, fr_reduce_weak(fr_sub8(ypx, ymx)), fr_select(q == 1, fr_reduce_weak(fr_add(ypx, ymx)), fr_select(q == 2, fr_reduce_weak(e), fr_zero())));
-  }
-#pragma unroll 1
-  for (int j = 62; j >= 0; j--) {
-    const int d = (int)((t[j >> 3] >> ((j & 7) * 4)) & 15u) - 8;
-    const Fr e = qtbl_load(tbl, d, q);           // issued ahead of the doublings
-#pragma unroll 1
-    for (int k = 0; k < 4; k++) c = quad_dbl(q, c);
-    c = quad_add(q, c, e);
-  }
-  // affine, back on the reference curve, canonical (epilogue_finish): x = X / (Z F), y = Y / Z
-  const Fr zi = fr_mul(fr_inv(quad_bcast<2>(c)), fr_one_plain());          // plain 1/Z
-  const Fr m = fr_select(q == 0, fr_mul(zi, c_K.FINV), zi);
-  const Fr v = fr_cond_sub_kr(fr_mul(c, m), R1);
+  recode_signed4(red, t);
+  const Fr top = quad_lift<false>(q, qtbl_load(tbl, signed4_digit(t, 63), q));   // (doublings follow)
+  const Fr c = quad_walk(tbl, t, 62, q, top);
+  const Fr v = quad_affine(q, c, fr_inv(quad_bcast<2>(c)));
   if (live && on && q < 2) {
     fr_to_words(v, w);
     store_w8(out + i * 64 + (size_t)q * 32, w);
@@ -151,8 +186,7 @@ __global__ void __launch_bounds__(BJJ_QUAD_BLOCK) bjj_k_mul_var_base_quad(const 
 namespace bjjk {
 // slow: the list K6 reads (reset by the caller), or nullptr when somebody else has made it (the scan of the split form)
 hipError_t mul_var_base_quad(hipStream_t st, const uint8_t* pts, const uint8_t* scalars, size_t n, uint8_t* out, u32* slow) {
-  const size_t grid = (n + BJJ_QUAD_ITEMS - 1) / BJJ_QUAD_ITEMS;
-  BJJ_LAUNCH(bjj_k_mul_var_base_quad, dim3((unsigned)(grid ? grid : 1)), dim3(BJJ_QUAD_BLOCK), 0, st, pts, scalars, n, out, slow);
+  BJJ_LAUNCH(bjj_k_mul_var_base_quad, grid_for(n, BJJ_QUAD_ITEMS), dim3(BJJ_QUAD_BLOCK), 0, st, pts, scalars, n, out, slow);
   return hipGetLastError();
 }
 }  // namespace bjjk
@@ -264,18 +298,6 @@ __global__ void __launch_bounds__(BJJ_P5C_BLOCK) bjj_k_poseidon5_coop(const uint
 // verdict, as with K4's bulk workgroups (k_verify.hip).
 // =====================================================================================================================================
 #define BJJ_VS_BLOCK 64
-__device__ __forceinline__ void qtbl_build(int q, u32* tbl, const Fr& c) {    // 0 .. 8 P for P = c (any Z): vb_build_table
-  const PNiels id = pniels_identity();
-  qtbl_store(tbl, 0, q, fr_select(q == 0, id.ymx, fr_select(q == 1, id.ypx, fr_select(q == 2, id.z2, id.t2d))));
-  const Fr p1 = quad_entry(q, c);
-  qtbl_store(tbl, 1, q, p1);
-  Fr cur = c;
-#pragma unroll 1
-  for (int k = 2; k <= 8; k++) {
-    cur = quad_add(q, cur, p1);
-    qtbl_store(tbl, k, q, quad_entry(q, cur));
-  }
-}
 // this lane's component of entry `slot` of the fixed-base table (load_niels: Y-X words 0..8, Y+X 9..17, 2D'xy 18..26; Z = 1: 2Z = 2), with the digit's sign
 __device__ __forceinline__ Fr qfb_load(const u32* __restrict__ table, size_t slot, bool neg, int q) {
   const int qq = (neg && q < 2) ? (q ^ 1) : q;
@@ -309,10 +331,94 @@ __device__ __forceinline__ void qfb_prefetch(const u32* __restrict__ table, int 
   for (int k = 0; k < 32; k++) sink ^= v[k];
   asm volatile("" ::"v"(sink));
 }
+// this lane's component of the entry the stream's next window names
+__device__ __forceinline__ Fr qfb_next(const u32* table, DigitStream& ds, int q) {
+  bool neg;
+  const size_t slot = digit_next(ds, neg);
+  return qfb_load(table, slot, neg, q);
+}
+// acc + the windows k .. nwin - 1 of the stream, cur = window k's entry: one quad addition per window, the next entry loaded one window ahead
+__device__ __forceinline__ Fr qfb_walk(const u32* table, DigitStream& ds, int k, int nwin, int q, Fr acc, Fr cur) {
+#pragma unroll 1
+  for (; k + 1 < nwin; k++) {
+    const Fr nxt = qfb_next(table, ds, q);                           // in flight during this window's addition
+    acc = quad_add(q, acc, cur);
+    cur = nxt;
+  }
+  return quad_add(q, acc, cur);
+}
+// acc + sc B8, sc < l (fixed_base_accumulate); window 0 is stored in T form: 2D'T = D' (2T) on lane 3
+__device__ __forceinline__ Fr quad_add_fixed_base(const u32* table, int W, int nwin, const u32 sc[8], int q, const Fr& acc) {
+  DigitStream ds = digit_stream(sc, W);
+  const Fr e0 = qfb_next(table, ds, q);
+  return qfb_walk(table, ds, 0, nwin, q, acc, fr_select(q == 3, fr_mul(e0, c_K.DP), e0));
+}
+// sc B8 from scratch, sc < l (fixed_base_mul): window 0's entry is lifted to a point -- it is stored in T form: (2x' : 2y : 2 : 2x'y) costs no multiplication
+__device__ __forceinline__ Fr quad_mul_fixed_base(const u32* table, int W, int nwin, const u32 sc[8], int q) {
+  DigitStream ds = digit_stream(sc, W);
+  const Fr e0 = qfb_next(table, ds, q);
+  const Fr ymx = quad_bcast<0>(e0), ypx = quad_bcast<1>(e0);
+  const Fr c = fr_select(q == 0, fr_reduce_weak(fr_sub(ypx, ymx)), fr_select(q == 1, fr_add(ypx, ymx), fr_select(q == 2, fr_add(fr_one(), fr_one()), fr_add(e0, fr_zero()))));
+  const Fr e1 = qfb_next(table, ds, q);
+  return qfb_walk(table, ds, 1, nwin, q, c, e1);
+}
+
+// ---- what the three verify kernels (and the signer, for the hash) share
+// H(a, b, c, d, e) (src/lib.rs:400-404 / :369) on six lanes of the group of eight whose lane gl this is; the hash (Montgomery) on every lane of the group
+__device__ __forceinline__ Fr p5c_hash5(int gl, const Fr& a, const Fr& b, const Fr& c, const Fr& d, const Fr& e) {
+  const int j = gl < 6 ? gl : 5;                                     // the spare lanes shadow lane 5 (their values are never read)
+  const Fr st0 = fr_select(j == 0, fr_zero(), fr_select(j == 1, a, fr_select(j == 2, b, fr_select(j == 3, c, fr_select(j == 4, d, e)))));
+  return grp_get(p5c_permute(j, gl, st0), 0);
+}
+// the signature of this lane's group of eight (lane = 0 .. 63 in the wave).  An item whose pk or R is off the curve (need_exact) is the exact launch's
+struct VerifySmallItem {
+  size_t i;                  // a group beyond the batch repeats the last item and stores nothing (live)
+  int live;                  // (an int: as a bool member the compiler meets it in the other polarity, and the kernels' register counts move by two)
+  bool msg_gt, need_exact;
+  Fr rx, ry, ax, ay, m5;     // R, pk (= A), msg: Montgomery
+};
+// w: eight words of the kernel's, the staging buffer of the loads -- declared in here its stack slot would end with this function and be shared, and the kernels' scratch and
+// registers would not be what they were with the loads written out
+__device__ __forceinline__ VerifySmallItem verify_small_item(int lane, const uint8_t* pk, const uint8_t* rb8, const uint8_t* msg, size_t n, u32 w[8]) {
+  VerifySmallItem it;
+  const size_t item = (size_t)blockIdx.x * (BJJ_VS_BLOCK / 8) + (size_t)(lane >> 3);
+  it.live = item < n;
+  it.i = it.live ? item : n - 1;
+  load_w8(msg + it.i * 32, w);
+  it.msg_gt = words_gt_modulus(w);                                   // :396-398 / :365-367
+  it.m5 = fr_to_mont_words(w);
+  load_w8(rb8 + it.i * 64, w);      it.rx = fr_to_mont_words(w);
+  load_w8(rb8 + it.i * 64 + 32, w); it.ry = fr_to_mont_words(w);
+  load_w8(pk + it.i * 64, w);       it.ax = fr_to_mont_words(w);
+  load_w8(pk + it.i * 64 + 32, w);  it.ay = fr_to_mont_words(w);
+  it.need_exact = !it.msg_gt && !(ref_on_curve(it.rx, it.ry, c_K) && ref_on_curve(it.ax, it.ay, c_K));
+  return it;
+}
+// the scalars of the EdDSA fast path (verify_fast_t), every lane for itself: the short odd pair (u, v) of hm mod l, cw = v s mod l for the fixed-base part, and jw, the
+// windows of the pair -- as many as the widest pair of the WAVE needs (joint_short_pair), so the trip count is wave-uniform and the same for both waves of the two-wave form.
+// s32: the signature's s; sw: eight words of the kernel's for it, declared there behind u and vmag (as w of verify_small_item: the frame keeps its layout)
+__device__ __forceinline__ void eddsa_scalars(const Fr& hm, const uint8_t* s32, u32 sw[8], Fr& u, Fr& vmag, bool& vneg, u32 cw[8], int& jw) {
+  const Fr hm_plain = fr_canon(fr_mul(hm, fr_one_plain()));
+  lattice_short_pair(plain_mod_l(hm_plain, c_K), u, vmag, vneg, c_K);
+  load_w8(s32, sw);
+  fr_to_words(verify_fb_scalar(sw, vmag, vneg, c_K), cw);
+  const int ub = limbs_bits(u), vb = limbs_bits(vmag);
+  const int mb = ub > vb ? ub : vb;
+  const int need = mb <= 2 ? 1 : (mb + 5) >> 2;
+  jw = wave_max_int(need > 64 ? 64 : need);
+}
+// the projective identity (0 : z : z)
+__device__ __forceinline__ bool quad_is_identity(const Fr& acc) {
+  const Fr X = quad_bcast<0>(acc), Y = quad_bcast<1>(acc), Z = quad_bcast<2>(acc);
+  return fr_is_zero(X) && fr_eq(Y, Z);
+}
+
 // TWO waves per workgroup share the curve arithmetic of their eight signatures (they are on different SIMDs: truly side by side, not in lock-step): both hash and
 // derive the scalars (the same work at the same time costs no time), then wave 0 builds the table of -8A and walks u over it, wave 1 builds the table of -+R, walks |v|
 // over it and adds the fixed-base windows; wave 1's sum goes through LDS to wave 0, which adds it to its own and tests for the identity.  One scalar per wave instead of
 // two in a joint loop: 128 doublings + 33 additions in sequence instead of 128 + 66, 11 table operations instead of 19 (profiles/r06_small_calls.txt).
+// Made of: verify_small_item, p5c_hash5, eddsa_scalars on both waves; per wave quad_from_ref_affine, qtbl_build, recode_signed4, quad_lift of window jw - 1, quad_walk;
+// wave 1 quad_add_fixed_base; wave 0 quad_is_identity.
 __global__ void __launch_bounds__(2 * BJJ_VS_BLOCK) bjj_k_eddsa_verify_small(const u32* __restrict__ table, int W, int nwin,
                                                                             const uint8_t* __restrict__ pk, const uint8_t* __restrict__ rb8,
                                                                             const uint8_t* __restrict__ sg, const uint8_t* __restrict__ msg, size_t n,
@@ -320,38 +426,21 @@ __global__ void __launch_bounds__(2 * BJJ_VS_BLOCK) bjj_k_eddsa_verify_small(con
   __shared__ u32 tbl_all[2 * (BJJ_VS_BLOCK / 4) * QTBL_ITEM_WORDS];    // one table per quad and wave: 41.5 KB
   __shared__ u32 xch[(BJJ_VS_BLOCK / 4) * 4 * NL];                     // wave 1's sum, one coordinate per lane
   const int role = threadIdx.x >> 6, lane = threadIdx.x & 63, gl = lane & 7, q = lane & 3;
-  const int j = gl < 6 ? gl : 5;
   u32* tbl = tbl_all + (role * (BJJ_VS_BLOCK / 4) + (lane >> 2)) * QTBL_ITEM_WORDS;
   u32* mine = xch + ((lane >> 2) * 4 + q) * NL;
-  const size_t item = (size_t)blockIdx.x * (BJJ_VS_BLOCK / 8) + (size_t)(lane >> 3);
-  const bool live = item < n;
-  const size_t i = live ? item : n - 1;
   u32 w[8];
-  load_w8(msg + i * 32, w);
-  const bool msg_gt = words_gt_modulus(w);                           // :396-398
-  const Fr m5 = fr_to_mont_words(w);
-  load_w8(rb8 + i * 64, w);      const Fr rx = fr_to_mont_words(w);
-  load_w8(rb8 + i * 64 + 32, w); const Fr ry = fr_to_mont_words(w);
-  load_w8(pk + i * 64, w);       const Fr ax = fr_to_mont_words(w);
-  load_w8(pk + i * 64 + 32, w);  const Fr ay = fr_to_mont_words(w);
-  const bool need_exact = !msg_gt && !(ref_on_curve(rx, ry, c_K) && ref_on_curve(ax, ay, c_K));
-  // hm = H(R.x, R.y, A.x, A.y, msg) (:400-404), six lanes
-  const Fr st0 = fr_select(j == 0, fr_zero(), fr_select(j == 1, rx, fr_select(j == 2, ry, fr_select(j == 3, ax, fr_select(j == 4, ay, m5)))));
-  const Fr hm = grp_get(p5c_permute(j, gl, st0), 0);
-  const Fr hm_plain = fr_canon(fr_mul(hm, fr_one_plain()));
-  // the short odd pair and the fixed-base scalar (verify_fast_t): every lane for itself
+  const VerifySmallItem it = verify_small_item(lane, pk, rb8, msg, n, w);
+  const Fr hm = p5c_hash5(gl, it.rx, it.ry, it.ax, it.ay, it.m5);      // H(R.x, R.y, A.x, A.y, msg) (:400-404)
   Fr u, vmag;
   bool vneg;
-  lattice_short_pair(plain_mod_l(hm_plain, c_K), u, vmag, vneg, c_K);
   u32 sw[8], cw[8];
-  load_w8(sg + i * 32, sw);
-  fr_to_words(verify_fb_scalar(sw, vmag, vneg, c_K), cw);
+  int jw;
+  eddsa_scalars(hm, sg + it.i * 32, sw, u, vmag, vneg, cw, jw);
   if (role) qfb_prefetch(table, W, nwin, cw);
   // this wave's point on the a' = -1 curve, one coordinate per lane, and its table: wave 0 -8A, wave 1 -sign(v) R
   {
-    const Fr px = role ? fr_select(vneg, rx, fr_neg(rx)) : fr_neg(ax), py = role ? ry : ay;
-    const Fr X = fr_mul(px, c_K.F);
-    Fr c = fr_select(q == 0, X, fr_select(q == 1, py, fr_select(q == 2, fr_one(), fr_mul(X, py))));
+    const Fr px = role ? fr_select(vneg, it.rx, fr_neg(it.rx)) : fr_neg(it.ax), py = fr_select(role != 0, it.ry, it.ay);
+    Fr c = quad_from_ref_affine(q, px, py);
     if (!role) {
 #pragma unroll 1
       for (int k = 0; k < 3; k++) c = quad_dbl(q, c);
@@ -359,44 +448,13 @@ __global__ void __launch_bounds__(2 * BJJ_VS_BLOCK) bjj_k_eddsa_verify_small(con
     qtbl_build(q, tbl, c);
   }
   __syncthreads();
-  // this wave's scalar over its table, as many windows as the widest pair of the wave needs (joint_short_pair: the same count for both waves)
-  const int ub = limbs_bits(u), vb = limbs_bits(vmag);
-  const int mb = ub > vb ? ub : vb;
-  const int need = mb <= 2 ? 1 : (mb + 5) >> 2;
-  const int jw = wave_max_int(need > 64 ? 64 : need);
+  // this wave's scalar over its table, jw windows: the same count for both waves
   u32 t[8];
   recode_signed4(role ? vmag : u, t);
-  Fr acc;
-  {
-    const int jj = jw - 1;
-    const int d = (int)((t[jj >> 3] >> ((jj & 7) * 4)) & 15u) - 8;
-    const Fr e = qtbl_load(tbl, d, q);
-    const Fr ymx = quad_bcast<0>(e), ypx = quad_bcast<1>(e);         // pniels_to_ext with T (additions may follow at once): 2T = (2D'T) / D'
-    acc = fr_select(q == 0, fr_reduce_weak(fr_sub8(ypx, ymx)), fr_select(q == 1, fr_reduce_weak(fr_add(ypx, ymx)),
-                    fr_select(q == 2, fr_reduce_weak(e), fr_mul(e, c_K.DPINV))));
-  }
-#pragma unroll 1
-  for (int jj = jw - 2; jj >= 0; jj--) {
-    const int d = (int)((t[jj >> 3] >> ((jj & 7) * 4)) & 15u) - 8;
-    const Fr e = qtbl_load(tbl, d, q);
-#pragma unroll 1
-    for (int k = 0; k < 4; k++) acc = quad_dbl(q, acc);
-    acc = quad_add(q, acc, e);
-  }
-  if (role) {  // + (v s mod l) B8: the fixed-base windows (fixed_base_accumulate); window 0 is stored in T form
-    DigitStream ds = digit_stream(cw, W);
-    bool neg;
-    size_t slot = digit_next(ds, neg);
-    Fr cur = qfb_load(table, slot, neg, q);
-    cur = fr_select(q == 3, fr_mul(cur, c_K.DP), cur);
-#pragma unroll 1
-    for (int k = 0; k + 1 < nwin; k++) {
-      slot = digit_next(ds, neg);
-      const Fr nxt = qfb_load(table, slot, neg, q);                   // in flight during this window's addition
-      acc = quad_add(q, acc, cur);
-      cur = nxt;
-    }
-    acc = quad_add(q, acc, cur);
+  Fr acc = quad_lift<true>(q, qtbl_load(tbl, signed4_digit(t, jw - 1), q));   // (additions may follow at once)
+  acc = quad_walk(tbl, t, jw - 2, q, acc);
+  if (role) {
+    acc = quad_add_fixed_base(table, W, nwin, cw, q, acc);             // + (v s mod l) B8
 #pragma unroll
     for (int k = 0; k < NL; k++) mine[k] = acc.v[k];
   }
@@ -406,199 +464,93 @@ __global__ void __launch_bounds__(2 * BJJ_VS_BLOCK) bjj_k_eddsa_verify_small(con
 #pragma unroll
     for (int k = 0; k < NL; k++) other.v[k] = mine[k];
     acc = quad_add(q, acc, quad_entry(q, other));
-    // the projective identity (0 : z : z)
-    const Fr X = quad_bcast<0>(acc), Y = quad_bcast<1>(acc), Z = quad_bcast<2>(acc);
-    const int verdict = (fr_is_zero(X) && fr_eq(Y, Z)) ? 1 : 0;
-    if (live && !need_exact && gl == 0) ok[i] = (uint8_t)(msg_gt ? 0 : verdict);
+    const int verdict = quad_is_identity(acc) ? 1 : 0;
+    if (it.live && !it.need_exact && gl == 0) ok[it.i] = (uint8_t)(it.msg_gt ? 0 : verdict);
   }
 }
 
 // ONE wave per eight signatures, both scalars in a joint loop (joint_mul_windowed): eight lanes per signature instead of sixteen -- the form for calls that put more than a
 // wave or two on every CU (2^12 ... 2^13 signatures), where lanes are what is scarce: 643 us per call at 2^12 against 897 for the two-wave form, which wins below (587 vs 627 at 2^11).
+// Made of: verify_small_item, p5c_hash5, eddsa_scalars, quad_from_ref_affine and qtbl_build twice, recode_signed4 twice, quad_lift of u's window jw - 1 (+ v's entry),
+// quad_walk_joint, quad_add_fixed_base, quad_is_identity.
 __global__ void __launch_bounds__(BJJ_VS_BLOCK) bjj_k_eddsa_verify_small_joint(const u32* __restrict__ table, int W, int nwin,
                                                                         const uint8_t* __restrict__ pk, const uint8_t* __restrict__ rb8,
                                                                         const uint8_t* __restrict__ sg, const uint8_t* __restrict__ msg, size_t n,
                                                                         uint8_t* __restrict__ ok) {
   __shared__ u32 tbl_all[(BJJ_VS_BLOCK / 4) * 2 * QTBL_ITEM_WORDS];    // two tables per quad: 41.5 KB
   const int lane = threadIdx.x, gl = lane & 7, q = lane & 3;
-  const int j = gl < 6 ? gl : 5;
   u32* tbl1 = tbl_all + (lane >> 2) * 2 * QTBL_ITEM_WORDS;
   u32* tbl2 = tbl1 + QTBL_ITEM_WORDS;
-  const size_t item = (size_t)blockIdx.x * (BJJ_VS_BLOCK / 8) + (size_t)(lane >> 3);
-  const bool live = item < n;
-  const size_t i = live ? item : n - 1;
   u32 w[8];
-  load_w8(msg + i * 32, w);
-  const bool msg_gt = words_gt_modulus(w);                           // :396-398
-  const Fr m5 = fr_to_mont_words(w);
-  load_w8(rb8 + i * 64, w);      const Fr rx = fr_to_mont_words(w);
-  load_w8(rb8 + i * 64 + 32, w); const Fr ry = fr_to_mont_words(w);
-  load_w8(pk + i * 64, w);       const Fr ax = fr_to_mont_words(w);
-  load_w8(pk + i * 64 + 32, w);  const Fr ay = fr_to_mont_words(w);
-  const bool need_exact = !msg_gt && !(ref_on_curve(rx, ry, c_K) && ref_on_curve(ax, ay, c_K));
-  // hm = H(R.x, R.y, A.x, A.y, msg) (:400-404), six lanes
-  const Fr st0 = fr_select(j == 0, fr_zero(), fr_select(j == 1, rx, fr_select(j == 2, ry, fr_select(j == 3, ax, fr_select(j == 4, ay, m5)))));
-  const Fr hm = grp_get(p5c_permute(j, gl, st0), 0);
-  const Fr hm_plain = fr_canon(fr_mul(hm, fr_one_plain()));
-  // the short odd pair and the fixed-base scalar (verify_fast_t): every lane for itself
+  const VerifySmallItem it = verify_small_item(lane, pk, rb8, msg, n, w);
+  const Fr hm = p5c_hash5(gl, it.rx, it.ry, it.ax, it.ay, it.m5);      // H(R.x, R.y, A.x, A.y, msg) (:400-404)
   Fr u, vmag;
   bool vneg;
-  lattice_short_pair(plain_mod_l(hm_plain, c_K), u, vmag, vneg, c_K);
   u32 sw[8], cw[8];
-  load_w8(sg + i * 32, sw);
-  fr_to_words(verify_fb_scalar(sw, vmag, vneg, c_K), cw);
+  int jw;
+  eddsa_scalars(hm, sg + it.i * 32, sw, u, vmag, vneg, cw, jw);
   qfb_prefetch(table, W, nwin, cw);
   // P1 = -8A, P2 = -sign(v) R on the a' = -1 curve, one coordinate per lane; their tables
   {
-    const Fr X = fr_mul(fr_neg(ax), c_K.F);
-    Fr c = fr_select(q == 0, X, fr_select(q == 1, ay, fr_select(q == 2, fr_one(), fr_mul(X, ay))));
+    Fr c = quad_from_ref_affine(q, fr_neg(it.ax), it.ay);
 #pragma unroll 1
     for (int k = 0; k < 3; k++) c = quad_dbl(q, c);
     qtbl_build(q, tbl1, c);
   }
-  {
-    const Fr X = fr_mul(fr_select(vneg, rx, fr_neg(rx)), c_K.F);
-    const Fr c = fr_select(q == 0, X, fr_select(q == 1, ry, fr_select(q == 2, fr_one(), fr_mul(X, ry))));
-    qtbl_build(q, tbl2, c);
-  }
+  qtbl_build(q, tbl2, quad_from_ref_affine(q, fr_select(vneg, it.rx, fr_neg(it.rx)), it.ry));
   __syncthreads();
-  // the joint windowed loop (joint_short_pair / joint_mul_windowed): as many windows as the widest pair of the wave needs
-  const int ub = limbs_bits(u), vb = limbs_bits(vmag);
-  const int mb = ub > vb ? ub : vb;
-  const int need = mb <= 2 ? 1 : (mb + 5) >> 2;
-  const int jw = wave_max_int(need > 64 ? 64 : need);
+  // the joint windowed loop (joint_short_pair / joint_mul_windowed) over jw windows
   u32 tu[8], tv[8];
   recode_signed4(u, tu);
   recode_signed4(vmag, tv);
-  Fr acc;
-  {
-    const int jj = jw - 1;
-    const int du = (int)((tu[jj >> 3] >> ((jj & 7) * 4)) & 15u) - 8;
-    const int dv = (int)((tv[jj >> 3] >> ((jj & 7) * 4)) & 15u) - 8;
-    const Fr e1 = qtbl_load(tbl1, du, q), e2 = qtbl_load(tbl2, dv, q);
-    const Fr ymx = quad_bcast<0>(e1), ypx = quad_bcast<1>(e1);       // pniels_to_ext with T (an addition follows): 2T = (2D'T) / D'
-    acc = fr_select(q == 0, fr_reduce_weak(fr_sub8(ypx, ymx)), fr_select(q == 1, fr_reduce_weak(fr_add(ypx, ymx)),
-                    fr_select(q == 2, fr_reduce_weak(e1), fr_mul(e1, c_K.DPINV))));
-    acc = quad_add(q, acc, e2);
-  }
-#pragma unroll 1
-  for (int jj = jw - 2; jj >= 0; jj--) {
-    const int du = (int)((tu[jj >> 3] >> ((jj & 7) * 4)) & 15u) - 8;
-    const int dv = (int)((tv[jj >> 3] >> ((jj & 7) * 4)) & 15u) - 8;
-    const Fr e1 = qtbl_load(tbl1, du, q), e2 = qtbl_load(tbl2, dv, q);
-#pragma unroll 1
-    for (int k = 0; k < 4; k++) acc = quad_dbl(q, acc);
-    acc = quad_add(q, acc, e1);
-    acc = quad_add(q, acc, e2);
-  }
-  // + (v s mod l) B8: the fixed-base windows (fixed_base_accumulate); window 0 is stored in T form
-  {
-    DigitStream ds = digit_stream(cw, W);
-    bool neg;
-    size_t slot = digit_next(ds, neg);
-    Fr cur = qfb_load(table, slot, neg, q);
-    cur = fr_select(q == 3, fr_mul(cur, c_K.DP), cur);
-#pragma unroll 1
-    for (int k = 0; k + 1 < nwin; k++) {
-      slot = digit_next(ds, neg);
-      const Fr nxt = qfb_load(table, slot, neg, q);                   // in flight during this window's addition
-      acc = quad_add(q, acc, cur);
-      cur = nxt;
-    }
-    acc = quad_add(q, acc, cur);
-  }
-  // the projective identity (0 : z : z)
-  const Fr X = quad_bcast<0>(acc), Y = quad_bcast<1>(acc), Z = quad_bcast<2>(acc);
-  const int verdict = (fr_is_zero(X) && fr_eq(Y, Z)) ? 1 : 0;
-  if (live && !need_exact && gl == 0) ok[i] = (uint8_t)(msg_gt ? 0 : verdict);
+  Fr acc = quad_lift<true>(q, qtbl_load(tbl1, signed4_digit(tu, jw - 1), q));   // (an addition follows)
+  acc = quad_add(q, acc, qtbl_load(tbl2, signed4_digit(tv, jw - 1), q));
+  acc = quad_walk_joint(tbl1, tbl2, tu, tv, jw - 2, q, acc);
+  acc = quad_add_fixed_base(table, W, nwin, cw, q, acc);               // + (v s mod l) B8
+  const int verdict = quad_is_identity(acc) ? 1 : 0;
+  if (it.live && !it.need_exact && gl == 0) ok[it.i] = (uint8_t)(it.msg_gt ? 0 : verdict);
 }
 
 // verify_schnorr (src/lib.rs:364-385) for SHORT calls: the fast path of verify_fast_t<true> on eight lanes -- hash input order (pk, R, msg), the hash NOT multiplied by 8,
 // hm (-A) over 64 signed windows with the accumulator on a quad, + (s mod l) B8, compared with R on the a' = -1 curve; verdict 2 = Err (msg > Q).
+// Made of: verify_small_item, p5c_hash5, quad_from_ref_affine, qtbl_build, recode_signed4, quad_lift of window 63, quad_walk over 62 .. 0, quad_add_fixed_base.
 __global__ void __launch_bounds__(BJJ_VS_BLOCK) bjj_k_schnorr_verify_small(const u32* __restrict__ table, int W, int nwin,
                                                                           const uint8_t* __restrict__ pk, const uint8_t* __restrict__ rb8,
                                                                           const uint8_t* __restrict__ sg, const uint8_t* __restrict__ msg, size_t n,
                                                                           uint8_t* __restrict__ ok) {
   __shared__ u32 tbl_all[(BJJ_VS_BLOCK / 4) * QTBL_ITEM_WORDS];
   const int lane = threadIdx.x, gl = lane & 7, q = lane & 3;
-  const int j = gl < 6 ? gl : 5;
   u32* tbl = tbl_all + (lane >> 2) * QTBL_ITEM_WORDS;
-  const size_t item = (size_t)blockIdx.x * (BJJ_VS_BLOCK / 8) + (size_t)(lane >> 3);
-  const bool live = item < n;
-  const size_t i = live ? item : n - 1;
   u32 w[8];
-  load_w8(msg + i * 32, w);
-  const bool msg_gt = words_gt_modulus(w);                           // :365-367
-  const Fr m5 = fr_to_mont_words(w);
-  load_w8(rb8 + i * 64, w);      const Fr rx = fr_to_mont_words(w);
-  load_w8(rb8 + i * 64 + 32, w); const Fr ry = fr_to_mont_words(w);
-  load_w8(pk + i * 64, w);       const Fr ax = fr_to_mont_words(w);
-  load_w8(pk + i * 64 + 32, w);  const Fr ay = fr_to_mont_words(w);
-  const bool need_exact = !msg_gt && !(ref_on_curve(rx, ry, c_K) && ref_on_curve(ax, ay, c_K));
-  const Fr st0 = fr_select(j == 0, fr_zero(), fr_select(j == 1, ax, fr_select(j == 2, ay, fr_select(j == 3, rx, fr_select(j == 4, ry, m5)))));   // :369
-  const Fr hm = grp_get(p5c_permute(j, gl, st0), 0);
+  const VerifySmallItem it = verify_small_item(lane, pk, rb8, msg, n, w);
+  const Fr hm = p5c_hash5(gl, it.ax, it.ay, it.rx, it.ry, it.m5);      // :369
   u32 kw[8], sw[8], sl[8];
   fr_to_words(fr_canon(fr_mul(hm, fr_one_plain())), kw);             // hm < r < 2^254: no reduction
-  load_w8(sg + i * 32, sw);
+  load_w8(sg + it.i * 32, sw);
   scalar_mod_l(sw, sl, c_K);                                         // B8 has order l
   qfb_prefetch(table, W, nwin, sl);
-  {
-    const Fr X = fr_mul(fr_neg(ax), c_K.F);                          // -A on the a' = -1 curve
-    qtbl_build(q, tbl, fr_select(q == 0, X, fr_select(q == 1, ay, fr_select(q == 2, fr_one(), fr_mul(X, ay)))));
-  }
+  qtbl_build(q, tbl, quad_from_ref_affine(q, fr_neg(it.ax), it.ay));   // -A
   __syncthreads();
   u32 t[8];
-  {
-    u64 cy = 0;
-#pragma unroll
-    for (int k = 0; k < 8; k++) { cy += (u64)kw[k] + 0x88888888u; t[k] = (u32)cy; cy >>= 32; }
-  }
-  Fr acc;
-  {
-    const int d = (int)((t[7] >> 28) & 15u) - 8;
-    const Fr e = qtbl_load(tbl, d, q);
-    const Fr ymx = quad_bcast<0>(e), ypx = quad_bcast<1>(e);
-    acc = fr_select(q == 0, fr_reduce_weak(fr_sub8(ypx, ymx)), fr_select(q == 1, fr_reduce_weak(fr_add(ypx, ymx)), fr_select(q == 2, fr_reduce_weak(e), fr_zero())));
-  }
-#pragma unroll 1
-  for (int jj = 62; jj >= 0; jj--) {
-    const int d = (int)((t[jj >> 3] >> ((jj & 7) * 4)) & 15u) - 8;
-    const Fr e = qtbl_load(tbl, d, q);
-#pragma unroll 1
-    for (int k = 0; k < 4; k++) acc = quad_dbl(q, acc);
-    acc = quad_add(q, acc, e);
-  }
-  {  // + (s mod l) B8 (:377)
-    DigitStream ds = digit_stream(sl, W);
-    bool neg;
-    size_t slot = digit_next(ds, neg);
-    Fr cur = qfb_load(table, slot, neg, q);
-    cur = fr_select(q == 3, fr_mul(cur, c_K.DP), cur);
-#pragma unroll 1
-    for (int k = 0; k + 1 < nwin; k++) {
-      slot = digit_next(ds, neg);
-      const Fr nxt = qfb_load(table, slot, neg, q);
-      acc = quad_add(q, acc, cur);
-      cur = nxt;
-    }
-    acc = quad_add(q, acc, cur);
-  }
+  recode_signed4(kw, t);
+  Fr acc = quad_lift<false>(q, qtbl_load(tbl, signed4_digit(t, 63), q));   // (doublings follow)
+  acc = quad_walk(tbl, t, 62, q, acc);
+  acc = quad_add_fixed_base(table, W, nwin, sl, q, acc);             // + (s mod l) B8 (:377)
   const Fr X = quad_bcast<0>(acc), Y = quad_bcast<1>(acc), Z = quad_bcast<2>(acc);
-  const int verdict = (fr_eq(X, fr_mul(fr_mul(rx, c_K.F), Z)) && fr_eq(Y, fr_mul(ry, Z))) ? 1 : 0;
-  if (live && !need_exact && gl == 0) ok[i] = (uint8_t)(msg_gt ? 2 : verdict);
+  const int verdict = (fr_eq(X, fr_mul(fr_mul(it.rx, c_K.F), Z)) && fr_eq(Y, fr_mul(it.ry, Z))) ? 1 : 0;
+  if (it.live && !it.need_exact && gl == 0) ok[it.i] = (uint8_t)(it.msg_gt ? 2 : verdict);
 }
 
 // =====================================================================================================================================
 // PrivateKey::sign (src/lib.rs:308-342) for SHORT calls: eight lanes per signature.  sign_item (sign.hpp) as it is -- the two Blake-512 digests, r, the two
 // fixed-base multiplications, one inversion -- on every lane of the group for itself, and the Poseidon hash, two thirds of the lane form's time, on six of them
-// (p5c_permute).  Same field elements, same outputs; the constant-time signer option keeps its own kernels.  C64: Signature::compress (k_sign.hip).
+// (p5c_hash5).  Same field elements, same outputs; the constant-time signer option keeps its own kernels.  C64: Signature::compress (k_sign.hip).
 // =====================================================================================================================================
 template <bool C64>
 __device__ __forceinline__ void sign_small_body(const u32* __restrict__ table, int W, int nwin, const uint8_t* __restrict__ keys,
                                                 const uint8_t* __restrict__ msgs, size_t n, uint8_t* __restrict__ out_r, uint8_t* __restrict__ out_s,
                                                 uint8_t* __restrict__ ok) {
   const int lane = threadIdx.x, gl = lane & 7;
-  const int j = gl < 6 ? gl : 5;
   const size_t item = (size_t)blockIdx.x * (BJJ_VS_BLOCK / 8) + (size_t)(lane >> 3);
   const bool live = item < n;
   const size_t i = live ? item : n - 1;
@@ -626,8 +578,7 @@ __device__ __forceinline__ void sign_small_body(const u32* __restrict__ table, i
   const Fr h0 = fr_mul(fr_mul(Rp.X, zr), c_K.FINV), h1 = fr_mul(Rp.Y, zr);
   const Fr h2 = fr_mul(fr_mul(Ap.X, za), c_K.FINV), h3 = fr_mul(Ap.Y, za);
   const Fr h4 = fr_to_mont_words(msg);                           // :321
-  const Fr st0 = fr_select(j == 0, fr_zero(), fr_select(j == 1, h0, fr_select(j == 2, h1, fr_select(j == 3, h2, fr_select(j == 4, h3, h4)))));
-  const Fr hm = grp_get(p5c_permute(j, gl, st0), 0);             // :332-333
+  const Fr hm = p5c_hash5(gl, h0, h1, h2, h3, h4);               // :332-333
   const Fr hm_plain = fr_canon(fr_mul(hm, fr_one_plain()));      // :336
   const Fr t = fl_mul(fr_from_words(pruned), c_K.L_R2, c_K);
   const Fr s = fl_canon4(fr_add(fl_mul(hm_plain, t, c_K), r), c_K);   // :335-339
@@ -656,11 +607,11 @@ __global__ void __launch_bounds__(BJJ_VS_BLOCK) bjj_k_sign_small_c64(SIGN_SMALL_
 // B8.mul_scalar(n) / PrivateKey::public (src/lib.rs:149-164, 304-306) for SHORT calls: four lanes per item.  fixed_base_mul (bjj_device.hpp) with the accumulator on a
 // quad: window 0's entry lifted to a point, one quad addition per further window (each table entry read one component per lane, all of them touched up front), then the
 // affine conversion of THIS item alone -- no workgroup-wide inversion, no stash -- and, with COMPRESS, Point::compress (src/lib.rs:166-178) of it.
+// Made of: qfb_prefetch, quad_mul_fixed_base (which shares qfb_walk with the verifiers' quad_add_fixed_base), quad_affine.
 // =====================================================================================================================================
 template <bool COMPRESS>
 __device__ __forceinline__ void fixed_base_quad_body(const u32* __restrict__ table, int W, int nwin, const uint8_t* __restrict__ scalars, size_t n,
                                                      uint8_t* __restrict__ out) {
-  constexpr u32 R1[NL] = {BJJ_N0, BJJ_N1, BJJ_N2, BJJ_N3, BJJ_N4, BJJ_N5, BJJ_N6, BJJ_N7, BJJ_N8};
   const int lane = threadIdx.x, q = lane & 3;
   const size_t item = (size_t)blockIdx.x * BJJ_QUAD_ITEMS + (size_t)(lane >> 2);
   const bool live = item < n;
@@ -669,28 +620,8 @@ __device__ __forceinline__ void fixed_base_quad_body(const u32* __restrict__ tab
   load_w8(scalars + i * 32, raw);
   scalar_mod_l(raw, sc, c_K);
   qfb_prefetch(table, W, nwin, sc);
-  DigitStream ds = digit_stream(sc, W);
-  bool neg;
-  size_t slot = digit_next(ds, neg);
-  Fr c;
-  {  // window 0 is stored in T form: (2x' : 2y : 2 : 2x'y) costs no multiplication (fixed_base_mul)
-    const Fr e0 = qfb_load(table, slot, neg, q);
-    const Fr ymx = quad_bcast<0>(e0), ypx = quad_bcast<1>(e0);
-    c = fr_select(q == 0, fr_reduce_weak(fr_sub(ypx, ymx)), fr_select(q == 1, fr_add(ypx, ymx), fr_select(q == 2, fr_add(fr_one(), fr_one()), fr_add(e0, fr_zero()))));
-  }
-  slot = digit_next(ds, neg);
-  Fr cur = qfb_load(table, slot, neg, q);
-#pragma unroll 1
-  for (int k = 1; k + 1 < nwin; k++) {
-    slot = digit_next(ds, neg);
-    const Fr nxt = qfb_load(table, slot, neg, q);
-    c = quad_add(q, c, cur);
-    cur = nxt;
-  }
-  c = quad_add(q, c, cur);
-  const Fr zi = fr_mul(fr_inv(quad_bcast<2>(c)), fr_one_plain());
-  const Fr m = fr_select(q == 0, fr_mul(zi, c_K.FINV), zi);
-  const Fr v = fr_cond_sub_kr(fr_mul(c, m), R1);                     // lane 0: x, lane 1: y, canonical
+  const Fr c = quad_mul_fixed_base(table, W, nwin, sc, q);
+  const Fr v = quad_affine(q, c, fr_inv(quad_bcast<2>(c)));   // lane 0: x, lane 1: y, canonical
   if (COMPRESS) {
     const int big = __builtin_amdgcn_mov_dpp((int)plain_gt_halfq(v, c_K), 0x00, 0xf, 0xf, true);   // lane 0's x > (Q - 1) / 2, on the quad
     if (live && q == 1) {
@@ -716,31 +647,28 @@ namespace bjjk {
 // the bulk of a short verify call; the scan (before) and the exact launch (behind) are K4's (k_verify.hip)
 hipError_t verify_small(hipStream_t st, bool schnorr, const u32* table, int W, int nwin, const uint8_t* pk, const uint8_t* rb8, const uint8_t* s, const uint8_t* msg,
                         size_t n, uint8_t* ok) {
-  const size_t per = BJJ_VS_BLOCK / 8, grid = (n + per - 1) / per;
-  if (schnorr) BJJ_LAUNCH(bjj_k_schnorr_verify_small, dim3((unsigned)(grid ? grid : 1)), dim3(BJJ_VS_BLOCK), 0, st, table, W, nwin, pk, rb8, s, msg, n, ok);
-  else if (n <= ((size_t)1 << 11))
-    BJJ_LAUNCH(bjj_k_eddsa_verify_small, dim3((unsigned)(grid ? grid : 1)), dim3(2 * BJJ_VS_BLOCK), 0, st, table, W, nwin, pk, rb8, s, msg, n, ok);
-  else
-    BJJ_LAUNCH(bjj_k_eddsa_verify_small_joint, dim3((unsigned)(grid ? grid : 1)), dim3(BJJ_VS_BLOCK), 0, st, table, W, nwin, pk, rb8, s, msg, n, ok);
+  const dim3 grid = grid_for(n, BJJ_VS_BLOCK / 8);
+  if (schnorr) BJJ_LAUNCH(bjj_k_schnorr_verify_small, grid, dim3(BJJ_VS_BLOCK), 0, st, table, W, nwin, pk, rb8, s, msg, n, ok);
+  else if (n <= ((size_t)1 << 11)) BJJ_LAUNCH(bjj_k_eddsa_verify_small, grid, dim3(2 * BJJ_VS_BLOCK), 0, st, table, W, nwin, pk, rb8, s, msg, n, ok);
+  else BJJ_LAUNCH(bjj_k_eddsa_verify_small_joint, grid, dim3(BJJ_VS_BLOCK), 0, st, table, W, nwin, pk, rb8, s, msg, n, ok);
   return hipGetLastError();
 }
 hipError_t mul_fixed_base_quad(hipStream_t st, const u32* table, int W, int nwin, const uint8_t* scalars, size_t n, uint8_t* out, bool compressed) {
-  const size_t grid = (n + BJJ_QUAD_ITEMS - 1) / BJJ_QUAD_ITEMS;
-  if (compressed) BJJ_LAUNCH(bjj_k_mul_fixed_base_quad_c32, dim3((unsigned)(grid ? grid : 1)), dim3(BJJ_QUAD_BLOCK), 0, st, table, W, nwin, scalars, n, out);
-  else BJJ_LAUNCH(bjj_k_mul_fixed_base_quad, dim3((unsigned)(grid ? grid : 1)), dim3(BJJ_QUAD_BLOCK), 0, st, table, W, nwin, scalars, n, out);
+  const dim3 grid = grid_for(n, BJJ_QUAD_ITEMS);
+  if (compressed) BJJ_LAUNCH(bjj_k_mul_fixed_base_quad_c32, grid, dim3(BJJ_QUAD_BLOCK), 0, st, table, W, nwin, scalars, n, out);
+  else BJJ_LAUNCH(bjj_k_mul_fixed_base_quad, grid, dim3(BJJ_QUAD_BLOCK), 0, st, table, W, nwin, scalars, n, out);
   return hipGetLastError();
 }
 // out_s == nullptr: the compressed form (out_r = 64-byte Signature::compress records), as bjjk::sign
 hipError_t sign_small(hipStream_t st, const u32* table, int W, int nwin, const uint8_t* keys, const uint8_t* msgs, size_t n, uint8_t* out_r, uint8_t* out_s,
                       uint8_t* ok) {
-  const size_t per = BJJ_VS_BLOCK / 8, grid = (n + per - 1) / per;
-  if (out_s) BJJ_LAUNCH(bjj_k_sign_small, dim3((unsigned)(grid ? grid : 1)), dim3(BJJ_VS_BLOCK), 0, st, table, W, nwin, keys, msgs, n, out_r, out_s, ok);
-  else BJJ_LAUNCH(bjj_k_sign_small_c64, dim3((unsigned)(grid ? grid : 1)), dim3(BJJ_VS_BLOCK), 0, st, table, W, nwin, keys, msgs, n, out_r, out_s, ok);
+  const dim3 grid = grid_for(n, BJJ_VS_BLOCK / 8);
+  if (out_s) BJJ_LAUNCH(bjj_k_sign_small, grid, dim3(BJJ_VS_BLOCK), 0, st, table, W, nwin, keys, msgs, n, out_r, out_s, ok);
+  else BJJ_LAUNCH(bjj_k_sign_small_c64, grid, dim3(BJJ_VS_BLOCK), 0, st, table, W, nwin, keys, msgs, n, out_r, out_s, ok);
   return hipGetLastError();
 }
 hipError_t poseidon5_coop(hipStream_t st, const uint8_t* in, size_t n, uint8_t* out) {
-  const size_t per = BJJ_P5C_BLOCK / BJJ_P5C_GROUP, grid = (n + per - 1) / per;
-  BJJ_LAUNCH(bjj_k_poseidon5_coop, dim3((unsigned)(grid ? grid : 1)), dim3(BJJ_P5C_BLOCK), 0, st, in, n, out);
+  BJJ_LAUNCH(bjj_k_poseidon5_coop, grid_for(n, BJJ_P5C_BLOCK / BJJ_P5C_GROUP), dim3(BJJ_P5C_BLOCK), 0, st, in, n, out);
   return hipGetLastError();
 }
 }  // namespace bjjk

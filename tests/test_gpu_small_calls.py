@@ -231,7 +231,8 @@ def test_verify_short_calls_every_verdict_against_the_lane_kernel_and_the_oracle
         assert 0 < (want == 0).sum() < nmax // 8 and (want[extra[5:10]] == 1).all()
         ref = k4.eddsa_verify(A, R, S, msg)
         assert k4.info().last_verify_dispatch in (0, 1) and (ref == want).all()
-        for n in (1, 2, 7, 8, 9, 63, 64, 65, 1000, VERIFY_SMALL_MAX - 1, VERIFY_SMALL_MAX, VERIFY_SMALL_MAX + 1, nmax):
+        for n in (1, 2, 7, 8, 9, 63, 64, 65, 1000, 2047, 2048, 2049,       # 2^11: two waves per eight signatures up to it, the joint form above (bjjk::verify_small)
+                  VERIFY_SMALL_MAX - 1, VERIFY_SMALL_MAX, VERIFY_SMALL_MAX + 1, nmax):
             got = ctx.eddsa_verify(A[:n], R[:n], S[:n], msg[:n])
             assert ctx.info().last_verify_dispatch == (2 if n <= VERIFY_SMALL_MAX else ctx.info().last_verify_dispatch), n
             assert (n <= VERIFY_SMALL_MAX) == (ctx.info().last_verify_dispatch == 2)
