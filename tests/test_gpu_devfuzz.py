@@ -382,7 +382,9 @@ def test_asm_dot_products(fz):
 
 def test_extended_coordinate_formulas(fz):
     """ext_madd / ext_add_pn / ext_dbl (a' = -1 curve) on the device: random points of the group in random projective
-    scalings and lazy (< 2r) coordinates, against the affine group law in Python integers; asm == portable bit for bit."""
+    scalings and lazy (< 2r) coordinates, against the affine group law in Python integers; asm == portable bit for bit.
+    Random points only: the exceptional pairs (P + (-P), P + P, P + O, torsion points), the extreme representatives and the
+    negated table entries are the directed test of tests/test_gpu_curve_ops.py (sets in tests/curve_ref.py)."""
     import random
     import torch
     rnd = random.Random(99)
