@@ -13,6 +13,11 @@
 #ifndef BJJ_DLOG_BLOCK
 #define BJJ_DLOG_BLOCK 1024
 #endif
+// Tag width of a slot.  The library ships 32; tests/devfuzz/dlog.hip compiles this unit again with 3, where false tag hits are the
+// rule and confirmation has something to refuse in every search.
+#ifndef BJJ_DLOG_TAG_BITS
+#define BJJ_DLOG_TAG_BITS 32
+#endif
 
 struct DlogSlotsRead {
   const unsigned long long* p;
@@ -45,7 +50,7 @@ __global__ void __launch_bounds__(BJJ_DLOG_BLOCK) bjj_k_dlog_build(unsigned long
 #pragma unroll 1
   for (u32 k = 0; k < chain; k++) {
     const Fr zinv = block_invert<BJJ_DLOG_BLOCK, INV_K1>(acc.Z, lds);
-    if (j0 + k < entries) lost += dlog_insert<32>(S, mask, (u32)(j0 + k), acc, zinv) ? 0 : 1;
+    if (j0 + k < entries) lost += dlog_insert<BJJ_DLOG_TAG_BITS>(S, mask, (u32)(j0 + k), acc, zinv) ? 0 : 1;
     acc = ext_madd(acc, g);
   }
   if (lost) atomicAdd(failed, lost);
@@ -57,7 +62,7 @@ __global__ void __launch_bounds__(BJJ_BLOCK) bjj_k_dlog_check_entries(const unsi
   unsigned long long mine = 0;
 #pragma unroll 1
   for (u64 j = (u64)blockIdx.x * blockDim.x + threadIdx.x; j < entries; j += nthreads)
-    mine += (unsigned long long)dlog_check_entry<32>(S, mask, params, (u32)j, b, c_K);
+    mine += (unsigned long long)dlog_check_entry<BJJ_DLOG_TAG_BITS>(S, mask, params, (u32)j, b, c_K);
   if (mine) atomicAdd(bad, mine);
 }
 // bad[0] += violated conditions, bad[1] += occupied slots
@@ -94,7 +99,7 @@ __global__ void __launch_bounds__(BJJ_DLOG_BLOCK) bjj_k_dlog_search(const unsign
 #pragma unroll 1
     while (__syncthreads_or(L.st == DL_SEARCH)) {
       const Fr zinv = block_invert<BJJ_DLOG_BLOCK, INV_K1>(L.Q.Z, lds);
-      dlog_step<32>(L, zinv, ns, S, mask, s1);
+      dlog_step<BJJ_DLOG_TAG_BITS>(L, zinv, ns, S, mask, s1);
     }
     if (!__syncthreads_or(L.st == DL_PENDING)) break;
     dlog_confirm(L, load_niels(params + DLOG_P_G), b, range_bits);

@@ -1,7 +1,8 @@
 // DEBUG HARNESS (tests only): the per-lane bodies of the discrete-logarithm kernels (csrc/dlog.hpp, what k_dlog.hip launches) on the
 // CPU with limb / value-bound assertions and a slot policy that refuses a slot outside the table -- a stand-alone program, so that
 // it also runs under AddressSanitizer and UndefinedBehaviorSanitizer as it is (tests/test_dlog_host.py builds it twice).  Not linked
-// into libbjj_hip.so.  Where the kernels take 1 / Z from the workgroup inversion, this program takes it from fr_inv.
+// into libbjj_hip.so.  Where the kernels take 1 / Z from the workgroup inversion, this program takes it from fr_inv.  A launch that
+// takes more rounds than a lane can need -- every step refused at every slot -- aborts: on the device such a lane would spin.
 //
 // stdin:  "G <x> <y>"                      the base point (hex, on the curve; coordinates >= r are reduced)
 //         "T <baby_bits> <chain>"          the table: built thread by thread, `chain` consecutive j per thread
@@ -12,9 +13,12 @@
 //         "base <x> <y>"                   the canonical record dlog_setup leaves
 //         "check <tag_bits> <bad> <occupied>"            the check bodies over the untouched table
 //         "flip <tag_bits> <tag|j> <bad>"                the same with one bit of one occupied slot flipped
-//         "r <tag_bits> <range_bits> <i> <ok> <m>"       item i searched in one go (m in hex)
-//         "s <tag_bits> <range_bits> <i> <ok> <m> <launches>"  the same search cut into launches of 3 giant steps, and how many of
-//                                                        them walked the item (a decided item is passed by)
+//         "slots <tag_bits> <slot>:<j + 1> ..."          the occupied slots of the table as built
+//         "r <tag_bits> <range_bits> <i> <ok> <m> <refused>"   item i searched in one go (m in hex), and the tag hits of this item
+//                                                        that confirmation refused
+//         "s <tag_bits> <range_bits> <i> <ok> <m> <launches> <refused>"  the same search cut into launches of 3 giant steps, how
+//                                                        many of them walked the item (a decided item is passed by), and the
+//                                                        refused hits over all of them
 //         "rejected <tag_bits> <count>"                  tag hits that confirmation refused, over all "r" searches
 #define BJJ_DEBUG_BOUNDS 1
 #include <stdio.h>
@@ -122,8 +126,13 @@ static void launch(std::vector<u64>& tv, const Words* rec, int range_bits, u32 s
   memcpy(r, rec[0].w, 32); memcpy(r + 8, rec[1].w, 32);
   DlogLane L;
   dlog_start(L, r, g_params, s0, K);
+  const unsigned long long cap = ((unsigned long long)(s1 - s0) + 1) * (tv.size() + 1);
+  unsigned long long rounds = 0;
   for (;;) {
-    while (L.st == DL_SEARCH) dlog_step<TB>(L, fr_inv(L.Q.Z), ns, S, mask, s1);
+    while (L.st == DL_SEARCH) {
+      if (++rounds > cap) { fprintf(stderr, "step count cap: a lane that does not advance\n"); abort(); }
+      dlog_step<TB>(L, fr_inv(L.Q.Z), ns, S, mask, s1);
+    }
     if (L.st != DL_PENDING) break;
     rejected += dlog_confirm(L, load_niels(g_params + DLOG_P_G), g_b, range_bits) ? 1 : 0;
   }
@@ -136,6 +145,10 @@ static void run(u32 chain, const std::vector<int>& ranges, const std::vector<Wor
   unsigned long long occ = 0;
   const unsigned long long bad = check<TB>(tv, &occ);
   printf("check %d %llu %llu\n", TB, bad, occ);
+  printf("slots %d", TB);
+  for (size_t i = 0; i < tv.size(); i++)
+    if (tv[i] != 0) printf(" %zu:%u", i, (u32)tv[i]);
+  printf("\n");
   size_t victim = 0;
   while (victim < tv.size() && tv[victim] == 0) victim++;
   if (victim == tv.size()) abort();
@@ -147,12 +160,14 @@ static void run(u32 chain, const std::vector<int>& ranges, const std::vector<Wor
     const u32 nsteps = dlog_steps(g_b, range_bits);
     for (size_t i = 0; i < ni; i++) {
       u64 m = 0; int ok = 0;
+      const unsigned long long before = rejected;
       launch<TB>(tv, &items[2 * i], range_bits, 0, nsteps, true, m, ok, rejected);
-      printf("r %d %d %zu %d %llx\n", TB, range_bits, i, ok, (unsigned long long)m);
+      printf("r %d %d %zu %d %llx %llu\n", TB, range_bits, i, ok, (unsigned long long)m, rejected - before);
       unsigned long long walked = 0;
+      unused = 0;
       for (u32 s0 = 0; s0 < nsteps; s0 += 3)
         launch<TB>(tv, &items[2 * i], range_bits, s0, s0 + 3 < nsteps ? s0 + 3 : nsteps, s0 + 3 >= nsteps, m, ok, unused, &walked);
-      printf("s %d %d %zu %d %llx %llu\n", TB, range_bits, i, ok, (unsigned long long)m, walked);
+      printf("s %d %d %zu %d %llx %llu %llu\n", TB, range_bits, i, ok, (unsigned long long)m, walked, unused);
     }
   }
   printf("rejected %d %llu\n", TB, rejected);
