@@ -148,6 +148,28 @@ BJJ_HD void scalar_mod_l(const u32 w[8], u32 out[8], const Consts& K) {
   s = fr_cond_sub_kr(s, K.L.v);
   fr_to_words(s, out);
 }
+// scalar_mod_l without its last conditional subtraction.  Contract: out is congruent to w mod l, out = w - q l with the q
+// above, and so 0 <= out < 1.17 l < 0.885 * 2^251.  That is enough for the signed recoding over the B8 table (n B8 depends on
+// n mod l alone): out has no bit above 250, and the top window of the fixed_nwin(W) windows starts at bit (nwin - 1) W <=
+// 251, so its digit is at most floor(0.885 * 2^251 / 2^((nwin - 1) W)) + 1 (the carry).  Where nwin W = 252 (W = 4, 12, 14, 28,
+// ...: the tightest case) that is floor(0.4425 * 2^W) + 1 <= 2^(W-1) for every W >= 4 (W = 4: floor(7.08) + 1 = 8); where
+// nwin W > 252 the window holds fewer bits still.  So the top digit is non-negative, in the table, and leaves no carry -- for
+// every 4 <= W <= 28 (tests/test_k1_weak_mod_l_host.py walks all of them).  Used by K1's overlap form alone.
+// The limb form takes the integer as fr_from_words gives it and its top byte (K1 builds the limbs from registers).
+BJJ_HD Fr scalar_mod_l_weak_limbs(Fr s, u32 top_byte, const Consts& K) {
+  const u32 q = (top_byte * 10834u) >> 16;  // <= 42
+  int64_t c = 0;
+#pragma unroll
+  for (int i = 0; i < NL; i++) {
+    c += (int64_t)s.v[i] - (int64_t)((u64)q * K.L.v[i]);
+    s.v[i] = (i < NL - 1) ? ((u32)c & MASK29) : (u32)c;
+    c >>= 29;
+  }
+  return s;
+}
+BJJ_HD void scalar_mod_l_weak(const u32 w[8], u32 out[8], const Consts& K) {
+  fr_to_words(scalar_mod_l_weak_limbs(fr_from_words(w), w[7] >> 24, K), out);
+}
 // signed digit j of sc (< l): returns the table slot, sets neg; carry threads through the windows LSB-first
 BJJ_HD size_t fixed_digit_slot(const u32 sc[8], int j, int W, u32& carry, bool& neg) {
   const u32 u = scalar_window(sc, j, W) + carry;

@@ -178,13 +178,26 @@ __device__ __forceinline__ void epilogue_run(Fr run, size_t n, size_t tid, size_
 #ifndef BJJ_GATHER_AUX_NBUF1
 #define BJJ_GATHER_AUX_NBUF1 0
 #endif
-template <int NBUF>
+// STRIP (K1's overlap form only; every other user keeps its code): the eight slot numbers a lane needs per gather come from
+// a 256-byte wave-private strip behind the wave's staging areas -- one ds_write_b32 and two ds_read_b128 -- instead of eight
+// ds_bpermute_b32.  The slot of lane j sits at word (j & 7) * 8 + (j >> 3), so the slots of the entries 8k + L/8, k = 0 .. 7,
+// of which lane L moves a chunk each, are the eight consecutive words from (L / 8) * 8.  The strip is rewritten by every
+// gather; a wave's LDS operations complete in the order they were issued, so the reads of the gather before are done when
+// the write lands, and the reads below follow the write: the compiler's own lgkmcnt waits order the rest.  No barrier.
+#define FB_STRIP_WORDS 64
+template <int NBUF, bool STRIP = false>
 struct GatherCoopLds {
   struct Pending {};
   static constexpr int kBuffers = NBUF;
   const u32* table;
-  u32* wlds;   // this wave's staging area
+  u32* wlds;   // this wave's staging area (STRIP: NBUF areas, then the slot strip)
   int lane;
+  __device__ __forceinline__ void strip_slots(u32 slot, u32 (&s)[8]) const {
+    u32* const strip = wlds + NBUF * FB_STAGE_WORDS;
+    strip[(lane & 7) * 8 + (lane >> 3)] = slot;
+    const U4 lo = ((const U4*)strip)[(lane >> 3) * 2], hi = ((const U4*)strip)[(lane >> 3) * 2 + 1];
+    s[0] = lo.x; s[1] = lo.y; s[2] = lo.z; s[3] = lo.w; s[4] = hi.x; s[5] = hi.y; s[6] = hi.z; s[7] = hi.w;
+  }
   // all 64 lanes run together under this policy: wave-wide maximum (butterfly over the lanes)
   static __device__ __forceinline__ int wave_max(int v) {
 #pragma unroll
@@ -192,10 +205,12 @@ struct GatherCoopLds {
     return v;
   }
   __device__ __forceinline__ void issue(size_t slot, Pending&, int buf) const {
+    u32 ss[8];
+    if (STRIP) strip_slots((u32)slot, ss);
 #pragma unroll
     for (int k = 0; k < 8; k++) {
       const int e = 8 * k + (lane >> 3);
-      const u32 s = (u32)__shfl((int)(u32)slot, e, 64);
+      const u32 s = STRIP ? ss[k] : (u32)__shfl((int)(u32)slot, e, 64);
       const int c = (lane & 7) ^ ((e >> 1) & 7);
       __builtin_amdgcn_global_load_lds(table + (size_t)s * NIELS_WORDS + c * 4,
                                        (__attribute__((address_space(3))) void*)(wlds + (NBUF > 1 ? buf : 0) * FB_STAGE_WORDS + k * (8 * NIELS_WORDS)),

@@ -33,6 +33,28 @@
 #ifndef BJJ_K1_EARLY_RECORD
 #define BJJ_K1_EARLY_RECORD 0
 #endif
+// What the overlap form's item boundary (BJJ_K1_PIPE_ITEM) no longer waits for or computes twice; each part has its own A/B
+// knob (profiles/r11_ab_k1_item_boundary.txt):
+//   BJJ_K1_LATE_SCALAR  the next scalar's load and the stash stores of the item before are issued BEHIND the two waits that
+//                       open an item, so that those wait for the two gathers alone
+//   BJJ_K1_FOLD_LIFT    the first addition takes Y - X, Y + X, 2Z straight from window 0's entry (twice y - x', twice y + x',
+//                       the constant 4): no lift to an extended point that the addition then takes apart again
+//   BJJ_K1_WEAK_MOD_L   the scalar is reduced without the last conditional subtraction (bjj_device.hpp: scalar_mod_l_weak)
+//   BJJ_K1_SLOT_STRIP   a gather's slot numbers go through a wave-private LDS strip (k_common.hpp: GatherCoopLds<2, true>)
+// All four on: +2.0 ... 2.2 % on two streams in four interleaved rounds; none loses alone (fold is the largest at about +1 %),
+// and the build is not faster without any of them.
+#ifndef BJJ_K1_LATE_SCALAR
+#define BJJ_K1_LATE_SCALAR 1
+#endif
+#ifndef BJJ_K1_FOLD_LIFT
+#define BJJ_K1_FOLD_LIFT 1
+#endif
+#ifndef BJJ_K1_WEAK_MOD_L
+#define BJJ_K1_WEAK_MOD_L 1
+#endif
+#ifndef BJJ_K1_SLOT_STRIP
+#define BJJ_K1_SLOT_STRIP 1
+#endif
 
 // ---------------------------------------------------------------------------
 // init: fixed-base table (layout and recoding: bjj_device.hpp "fixed base").
@@ -77,11 +99,25 @@ struct K1Item {
   DigitStream ds;
   bool neg0, neg1;
 };
+// fr_from_words on the two loaded vectors, word by word from registers.  Through an array of eight words the compiler fetches
+// the word pairs that straddle a limb as vectors at odd offsets, keeps the array in scratch for that, and every item began
+// with a store to scratch, a load back and a wait for it.
+__device__ __forceinline__ u32 k1_limb(u32 lo, u32 hi, int sh) { return ((lo >> sh) | (hi << (32 - sh))) & MASK29; }
+__device__ __forceinline__ Fr k1_scalar_limbs(const U4 (&v)[2]) {
+  Fr s;
+  s.v[0] = v[0].x & MASK29;
+  s.v[1] = k1_limb(v[0].x, v[0].y, 29); s.v[2] = k1_limb(v[0].y, v[0].z, 26); s.v[3] = k1_limb(v[0].z, v[0].w, 23);
+  s.v[4] = k1_limb(v[0].w, v[1].x, 20); s.v[5] = k1_limb(v[1].x, v[1].y, 17); s.v[6] = k1_limb(v[1].y, v[1].z, 14);
+  s.v[7] = k1_limb(v[1].z, v[1].w, 11);
+  s.v[8] = v[1].w >> 8;
+  return s;
+}
 template <class G>
 __device__ __forceinline__ K1Item k1_item_begin(const G& g, int W, const U4 (&scalar)[2]) {
-  const u32 raw[8] = {scalar[0].x, scalar[0].y, scalar[0].z, scalar[0].w, scalar[1].x, scalar[1].y, scalar[1].z, scalar[1].w};
   u32 sc[8];
-  scalar_mod_l(raw, sc, c_K);
+  Fr s = scalar_mod_l_weak_limbs(k1_scalar_limbs(scalar), scalar[1].w >> 24, c_K);
+  if (!BJJ_K1_WEAK_MOD_L) s = fr_cond_sub_kr(s, c_K.L.v);   // scalar_mod_l
+  fr_to_words(s, sc);
   K1Item it;
   it.ds = digit_stream(sc, W);
   typename G::Pending p;
@@ -89,23 +125,86 @@ __device__ __forceinline__ K1Item k1_item_begin(const G& g, int W, const U4 (&sc
   g.issue(digit_next(it.ds, it.neg1), p, 1);
   return it;
 }
-template <class G>
-__device__ __forceinline__ void k1_item_windows(const G& g, int nwin, K1Item& it, Ext& acc, Niels& cur) {
+#if BJJ_K1_FOLD_LIFT
+// The accumulator between two additions as ext_madd first forms it: Y - X, Y + X and 2Z (lazy) and T.  Kept in this shape the
+// window loop stays rolled, does per trip exactly what ext_madd does, and window 0's entry (x', y) -- in T form -- IS a
+// state: Y - X = 2(y - x'), Y + X = 2(y + x'), 2Z = 4, T = 2x'y of the point (2x' : 2y : 2 : 2x'y) that fixed_base_mul lifts it to.
+struct K1Acc { Fr ym, yp, d, T; };
+// ext_madd on that state.  Operand bounds as in curve.hpp: ym < 6r with limbs < 1.5 * 2^30, yp < 4r and d < 4r with limbs
+// < 2^30, T N-form; the entry N-form < 2r but for t2d, which may be a lazy negation (limbs < 2^30, < 4r).
+template <bool NEED_T = true>
+__device__ __forceinline__ Ext k1_madd(const K1Acc& s, const Niels& q) {
+  Fr a = fr_mul(s.ym, q.ymx);
+  Fr b = fr_mul(s.yp, q.ypx);
+  Fr c = fr_mul(s.T, q.t2d);
+  Fr e = fr_sub_lazy(b, a);                      // < 6r,  limbs < 1.5*2^30
+  Fr f = fr_sub(s.d, c);                         // < 8r,  carried
+  Fr g = fr_add_lazy(s.d, c);                    // < 6r,  limbs < 1.5*2^30
+  Fr h = fr_add_lazy(b, a);                      // < 4r,  limbs < 2^30
+  Ext r;
+  r.X = fr_mul(e, f); r.Y = fr_mul(g, h); r.Z = fr_mul(f, g);
+  if (NEED_T) r.T = fr_mul(e, h); else r.T = fr_zero();
+  return r;
+}
+__device__ __forceinline__ K1Acc k1_forms(const Ext& p) {   // p's coordinates N-form < 2r (products)
+  K1Acc s;
+  s.ym = fr_sub_lazy(p.Y, p.X); s.yp = fr_add_lazy(p.Y, p.X); s.d = fr_add_lazy(p.Z, p.Z); s.T = p.T;
+  return s;
+}
+#else
+typedef Ext K1Acc;
+template <bool NEED_T = true>
+__device__ __forceinline__ Ext k1_madd(const K1Acc& s, const Niels& q) { return ext_madd<NEED_T>(s, q); }
+__device__ __forceinline__ K1Acc k1_forms(const Ext& p) { return p; }
+#endif
+// `mid` runs once both staged entries are in registers: the place for memory traffic that the two waits must not cover.
+template <class G, class MID>
+__device__ __forceinline__ void k1_item_windows(const G& g, int nwin, K1Item& it, K1Acc& acc, Niels& cur, const MID& mid) {
   typename G::Pending p;
   bool neg;
+#if BJJ_K1_FOLD_LIFT
+  const Niels e0 = g.finish(p, 0);
+  const Fr ymx0 = fr_select(it.neg0, e0.ypx, e0.ymx), ypx0 = fr_select(it.neg0, e0.ymx, e0.ypx);
+  acc.ym = fr_add_lazy(ymx0, ymx0);              // twice an N-form entry < 2r: lazy sums, limbs < 2^30, < 4r
+  acc.yp = fr_add_lazy(ypx0, ypx0);
+  acc.d = fr_add(fr_add(fr_one(), fr_one()), fr_add(fr_one(), fr_one()));   // the constant 4: N-form, < 4r
+  acc.T = e0.t2d;                                // N-form as stored; window 0's sign goes to window 1's t2d: C = T * t2d
+  BJJ_SCHED_FENCE();
+  const Niels e1 = g.finish(p, 1);
+  cur = niels_cneg_lazy(e1, it.neg1);
+  cur.t2d = fr_select(it.neg0 != it.neg1, fr_sub_lazy(fr_zero(), e1.t2d), e1.t2d);
+#else
   const Niels n0 = niels_cneg_lazy(g.finish(p, 0), it.neg0);
   acc.X = fr_reduce_weak(fr_sub(n0.ypx, n0.ymx));  // window 0 lifted to (2x' : 2y : 2 : 2x'y), as fixed_base_mul
   acc.Y = fr_add(n0.ypx, n0.ymx);
   acc.Z = fr_add(fr_one(), fr_one()); acc.T = fr_add(n0.t2d, fr_zero());
   BJJ_SCHED_FENCE();
   cur = niels_cneg_lazy(g.finish(p, 1), it.neg1);
+#endif
+  mid();
 #pragma unroll 1
   for (int j = 1; j + 1 < nwin; j++) {
     g.issue(digit_next(it.ds, neg), p, (j + 1) & 1);
-    acc = ext_madd(acc, cur);
+    acc = k1_forms(k1_madd(acc, cur));
     BJJ_SCHED_FENCE();
     cur = niels_cneg_lazy(g.finish(p, (j + 1) & 1), neg);
   }
+}
+// epilogue_stash (k_common.hpp) in two halves: the four packed values of an item wait in registers until its stores may go.
+struct K1Stash { U4 x[2], y[2], z[2], p[2]; };
+__device__ __forceinline__ void k1_stash_words(U4 (&v)[2], const Fr& f) {
+  u32 w[8];
+  fr_to_words(f, w);
+  v[0] = U4{w[0], w[1], w[2], w[3]}; v[1] = U4{w[4], w[5], w[6], w[7]};
+}
+__device__ __forceinline__ void k1_stash_pack(K1Stash& s, const Ext& p, Fr& run) {
+  k1_stash_words(s.x, p.X); k1_stash_words(s.y, p.Y); k1_stash_words(s.z, p.Z); k1_stash_words(s.p, run);
+  run = fr_mul(run, p.Z);
+}
+__device__ __forceinline__ void k1_stash_store(const K1Stash& s, uint8_t* xy_item, u32* scr_item) {
+  U4 *q = (U4*)xy_item, *r = (U4*)scr_item;
+  q[0] = s.x[0]; q[1] = s.x[1]; q[2] = s.y[0]; q[3] = s.y[1];
+  r[0] = s.z[0]; r[1] = s.z[1]; r[2] = s.p[0]; r[3] = s.p[1];
 }
 // An item's phase-1 record in registers, and epilogue_finish's arithmetic on it: loading and finishing apart, so that the
 // loads of one record run under the multiplications of another.
@@ -183,11 +282,13 @@ __device__ __forceinline__ void mul_fixed_base_body(const u32* __restrict__ tabl
                                                     size_t n, uint8_t* __restrict__ out, u32* __restrict__ scratch,
                                                     uint8_t* __restrict__ xy = nullptr) {
   __shared__ u32 lds[NL * 64];
-  __shared__ __attribute__((aligned(16))) u32 stage[(BLOCK / 64) * NBUF * FB_STAGE_WORDS];
+  constexpr bool STRIP = AHEAD && BJJ_K1_PIPE_ITEM && BJJ_K1_SLOT_STRIP;   // the overlap form's gather: k_common.hpp
+  constexpr int WAVE_WORDS = NBUF * FB_STAGE_WORDS + (STRIP ? FB_STRIP_WORDS : 0);
+  __shared__ __attribute__((aligned(16))) u32 stage[(BLOCK / 64) * WAVE_WORDS];
   const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t nthreads = (size_t)gridDim.x * blockDim.x;
   const int lane = threadIdx.x & 63;
-  const GatherCoopLds<NBUF> fb = {table, stage + (threadIdx.x >> 6) * NBUF * FB_STAGE_WORDS, lane};
+  const GatherCoopLds<NBUF, STRIP> fb = {table, stage + (threadIdx.x >> 6) * WAVE_WORDS, lane};
   uint8_t* const stash = (FORM & EPI_COMPRESS) ? xy : out;
   Fr run = fr_one();
   if (AHEAD && BJJ_K1_PIPE_ITEM) {
@@ -197,18 +298,33 @@ __device__ __forceinline__ void mul_fixed_base_body(const u32* __restrict__ tabl
       const U4* const sc4 = (const U4*)scalars;
       U4 raw[2] = {sc4[2 * (i < n ? i : n - 1)], sc4[2 * (i < n ? i : n - 1) + 1]};
       K1Item it = k1_item_begin(fb, W, raw);
+      // BJJ_K1_LATE_SCALAR: an item opens with two waits for ALL of the wave's memory traffic (one counter), meant for its two
+      // gathers, which were issued an addition earlier.  So nothing else is in flight then: the stash of the item before
+      // waits packed in `held` (32 registers, over a span without a multiplication) and is stored behind those waits, where
+      // the next scalar is requested as well; the first wait to cover either is the one that ends the first window trip.
+      K1Stash held = {};
+      bool pending = false;   // wave-uniform
+      size_t iheld = 0;
 #pragma unroll 1
       for (;;) {
         const size_t inext = i + nthreads, iload = inext < n ? inext : n - 1;   // a lane without a next item clamps
         const bool more = inext - lane < n;
-        if (more) { raw[0] = sc4[2 * iload]; raw[1] = sc4[2 * iload + 1]; }    // the next scalar: in flight under this item's windows
-        Ext acc;
+        if (!BJJ_K1_LATE_SCALAR && more) { raw[0] = sc4[2 * iload]; raw[1] = sc4[2 * iload + 1]; }
+        K1Acc acc;
         Niels cur;
-        k1_item_windows(fb, nwin, it, acc, cur);
+        k1_item_windows(fb, nwin, it, acc, cur, [&]() {
+          if (!BJJ_K1_LATE_SCALAR) return;
+          if (pending) k1_stash_store(held, stash + iheld * 64, scratch + iheld * 16);
+          if (more) { raw[0] = sc4[2 * iload]; raw[1] = sc4[2 * iload + 1]; }  // the next scalar: in flight under this item's windows
+        });
         if (more) it = k1_item_begin(fb, W, raw);                               // its first two gathers: under the last addition
         BJJ_SCHED_FENCE();
-        const Ext p = ext_madd<false>(acc, cur);  // the last window's addition, T not needed by the epilogue
-        if (i < n) epilogue_stash(p, run, stash + i * 64, scratch + i * 16);
+        const Ext p = k1_madd<false>(acc, cur);   // the last window's addition, T not needed by the epilogue
+        // a wave with a next item has this one in every lane (inext - lane < n and lane < nthreads give i < n): its stash is held
+        // back; a lane's last item has no wait behind it to hide under and is stored at once
+        pending = BJJ_K1_LATE_SCALAR && more;
+        if (pending) { k1_stash_pack(held, p, run); iheld = i; }
+        else if (i < n) epilogue_stash(p, run, stash + i * 64, scratch + i * 16);
         if (!more) break;
         i = inext;
       }
