@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import pack, unpack
+from dispatch_forms import LANE, SHORT, lane_ctx, make_lane_ctx, ran  # noqa: F401  (lane_ctx: the fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -82,7 +83,7 @@ def test_reference_chained_add_equals_mul_scalar_3(gpu_ctx, golden):
 
 # ---------------------------------------------------------------- scalars wider than 256 bits
 @pytest.mark.parametrize("nbytes", [64, 128, 352])
-def test_wide_scalars_on_and_off_curve(gpu_ctx, oracle, nbytes):
+def test_wide_scalars_on_and_off_curve(gpu_ctx, lane_ctx, oracle, nbytes):  # noqa: F811
     from babyjubjub_rs_amd import workload as w
     n = 130
     k = nbytes // 32
@@ -96,10 +97,16 @@ def test_wide_scalars_on_and_off_curve(gpu_ctx, oracle, nbytes):
     pts[4] = pack([(0, 1)])                     # identity
     pts[5] = pack([(0, Q - 1)])                 # order 2
     got = gpu_ctx.mul_var_base_wide(pts, sc, nbytes)
+    ran(gpu_ctx, "var", LANE)                   # scalars beyond 32 bytes run K2 at every size
     want = _mul_scalar_oracle(oracle, pts, sc, nbytes)
     assert (got == want).all(), np.nonzero((got != want).any(axis=1))[0][:8]
-    # the 32-byte record through the wide entry is the plain entry
-    assert (gpu_ctx.mul_var_base_wide(pts, sc[:, :32].copy(), 32) == gpu_ctx.mul_var_base(pts, sc[:, :32].copy())).all()
+    # the 32-byte record through the wide entry is the plain entry: a short call, four lanes per item; and K2 on the same records
+    plain = gpu_ctx.mul_var_base(pts, sc[:, :32].copy())
+    ran(gpu_ctx, "var", SHORT)
+    assert (gpu_ctx.mul_var_base_wide(pts, sc[:, :32].copy(), 32) == plain).all()
+    ran(gpu_ctx, "var", SHORT)
+    assert (lane_ctx.mul_var_base_wide(pts, sc[:, :32].copy(), 32) == plain).all() and (lane_ctx.mul_var_base(pts, sc[:, :32].copy()) == plain).all()
+    ran(lane_ctx, "var", LANE)
 
 
 def test_point_mul_scalar_wide_bigint(gpu_ctx, golden):
@@ -128,6 +135,10 @@ def test_default_window_is_modest(gpu_ctx, oracle):
         assert info.init_ms > 0
         sc = w.scalars_254(500, offset=31)
         assert (ctx.mul_fixed_base(sc) == oracle.mul_fixed_base(sc)).all()
+        ran(ctx, "fixed", SHORT)                # 500 items: four lanes per item; K1 over the same table past the threshold of 2^15
+        big = w.scalars_254((1 << 15) + 500, offset=31)
+        assert (ctx.mul_fixed_base(big) == oracle.mul_fixed_base(big)).all()
+        ran(ctx, "fixed", LANE)
     finally:
         ctx.close()
 

@@ -15,7 +15,10 @@ sum has a vanishing denominator, bjj_mul_var_base on every edge point times ever
 last_var_base_form 0 or 1), one call of the items as they are and one-item calls, which run the four-lane short-call
 kernel of k_small.hip (form 2).  No single point doubles into a vanishing
 denominator (tests/test_curve_ops_host.py::test_no_point_doubles_into_a_vanishing_denominator shows why), so that case keeps to
-the pair form.  Needs a real MI355X: `pytest -m gpu`."""
+the pair form.
+The short-call kernel's own group law, table and ladder -- the four-lane functions of k_small.hip, which part (2) reaches with
+canonical affine inputs only -- are driven on raw limbs, with these sets, by tests/test_gpu_quad_ops.py (tests/devfuzz/quad.hip,
+tests/quad_ref.py), and compared limb for limb with the lane functions of part (1).  Needs a real MI355X: `pytest -m gpu`."""
 import ctypes
 import os
 import random

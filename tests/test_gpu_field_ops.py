@@ -18,6 +18,7 @@ import pytest
 
 import field_ref as fr
 from conftest import ROOT, pack
+from dispatch_forms import LANE, SHORT, lane_ctx, ran  # noqa: F401  (lane_ctx: the fixture)
 from test_field_ops_host import flib  # noqa: F401  (the fixture that builds the CPU library of the same dispatcher)
 
 pytestmark = pytest.mark.gpu
@@ -113,20 +114,25 @@ def poseidon_edge_rows():
     return rows
 
 
-def test_abi_poseidon5_inputs_at_multiples_of_r(gpu_ctx, oracle):
+def test_abi_poseidon5_inputs_at_multiples_of_r(gpu_ctx, lane_ctx, oracle):  # noqa: F811
     """inputs >= r are reduced mod r (include/bjj_hip.h): the hash of the row equals the hash of the row reduced in plain
-    integers -- the model's expectation -- and the C oracle's hash of the row as it is"""
+    integers -- the model's expectation -- and the C oracle's hash of the row as it is.  Every call here is a short one, which
+    the session's context runs six lanes per hash (last_poseidon_form 1); the rows go through a context whose short calls run
+    one hash per lane (0), the kernel of the large calls, as well"""
     rows = poseidon_edge_rows()
     raw = _bytes_rows(rows, 5)
     want = oracle.poseidon5(_bytes_rows([tuple(v % R_MOD for v in row) for row in rows], 5))
     assert (oracle.poseidon5(raw) == want).all()
-    got = gpu_ctx.poseidon5(raw)                                              # one call
-    bad = np.nonzero((got != want).any(axis=1))[0]
-    assert bad.size == 0, [rows[i] for i in bad[:3]]
+    for ctx, form in ((gpu_ctx, SHORT), (lane_ctx, LANE)):
+        got = ctx.poseidon5(raw)                                              # one call
+        ran(ctx, "poseidon", form)
+        bad = np.nonzero((got != want).any(axis=1))[0]
+        assert bad.size == 0, (form, [rows[i] for i in bad[:3]])
     for i in range(len(rows)):                                                # row by row: the short-call kernels
         assert (gpu_ctx.poseidon5(raw[i:i + 1]) == want[i:i + 1]).all(), rows[i]
     for i in range(0, len(rows) - 5, 7):                                      # and a few rows at a time
         assert (gpu_ctx.poseidon5(raw[i:i + 5]) == want[i:i + 5]).all(), i
+    ran(gpu_ctx, "poseidon", SHORT)
 
 
 def test_abi_compress_points_edges(gpu_ctx, oracle):

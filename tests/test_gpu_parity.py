@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 from conftest import pack, unpack
+from dispatch_forms import LANE, SHORT, both, lane_ctx, ran  # noqa: F401  (lane_ctx: the fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -21,26 +22,34 @@ def rows(cases, key):
 
 
 # ---------------------------------------------------------------- golden fixtures
-def test_golden_fixed_base(gpu_ctx, golden):
+# The golden vectors and the seeded batches below are short calls: the session's context runs them on the several-lanes-per-item
+# kernels of k_small.hip, `lane_ctx` on the one-item-per-lane kernels; every test says which form each call took.
+def test_golden_fixed_base(gpu_ctx, lane_ctx, golden):  # noqa: F811
     fb = golden["oracle_vectors"]["fixed_base"]
-    got = gpu_ctx.mul_fixed_base(rows(fb, "n"))
-    assert (got.reshape(-1) == rows(fb, "out")).all()
+    for ctx, form in both(gpu_ctx, lane_ctx):
+        got = ctx.mul_fixed_base(rows(fb, "n"))
+        ran(ctx, "fixed", form)
+        assert (got.reshape(-1) == rows(fb, "out")).all()
 
 
-def test_golden_var_base_incl_off_curve(gpu_ctx, golden):
+def test_golden_var_base_incl_off_curve(gpu_ctx, lane_ctx, golden):  # noqa: F811
     vb = golden["oracle_vectors"]["var_base"]
     assert any(not c["on_curve"] for c in vb) and any(c["on_curve"] for c in vb)
-    got = gpu_ctx.mul_var_base(rows(vb, "p"), rows(vb, "n"))
-    want = rows(vb, "out").reshape(-1, 64)
-    bad = [i for i in range(len(vb)) if (got[i] != want[i]).any()]
-    assert not bad, [vb[i] for i in bad[:3]]
+    for ctx, form in both(gpu_ctx, lane_ctx):
+        got = ctx.mul_var_base(rows(vb, "p"), rows(vb, "n"))
+        ran(ctx, "var", form)
+        want = rows(vb, "out").reshape(-1, 64)
+        bad = [i for i in range(len(vb)) if (got[i] != want[i]).any()]
+        assert not bad, (form, [vb[i] for i in bad[:3]])
 
 
-def test_golden_poseidon(gpu_ctx, golden):
+def test_golden_poseidon(gpu_ctx, lane_ctx, golden):  # noqa: F811
     ps = golden["oracle_vectors"]["poseidon5"] + [
         {"in": c["in"], "out": c["out"]} for c in golden["reference_kats"]["poseidon_public"]["cases"]]
-    got = gpu_ctx.poseidon5(rows(ps, "in"))
-    assert (got.reshape(-1) == rows(ps, "out")).all()
+    for ctx, form in both(gpu_ctx, lane_ctx):
+        got = ctx.poseidon5(rows(ps, "in"))
+        ran(ctx, "poseidon", form)
+        assert (got.reshape(-1) == rows(ps, "out")).all()
 
 
 def test_golden_point_add(gpu_ctx, golden):
@@ -49,20 +58,25 @@ def test_golden_point_add(gpu_ctx, golden):
     assert (got.reshape(-1) == rows(ad, "out")).all()
 
 
-def test_golden_verify_edge_semantics(gpu_ctx, golden):
+def test_golden_verify_edge_semantics(gpu_ctx, lane_ctx, golden):  # noqa: F811
     ve = golden["oracle_vectors"]["verify"]
-    got = gpu_ctx.eddsa_verify(rows(ve, "pk"), rows(ve, "r_b8"), rows(ve, "s"), rows(ve, "msg"))
-    for c, g in zip(ve, got):
-        assert bool(g) == c["ok"], c["note"]
+    for ctx, form in both(gpu_ctx, lane_ctx):
+        got = ctx.eddsa_verify(rows(ve, "pk"), rows(ve, "r_b8"), rows(ve, "s"), rows(ve, "msg"))
+        ran(ctx, "verify", form)
+        for c, g in zip(ve, got):
+            assert bool(g) == c["ok"], (form, c["note"])
 
 
 # ---------------------------------------------------------------- seeded random vs oracle
 @pytest.mark.parametrize("n", [1, 63, 64, 65, 257, 4096])
-def test_fixed_base_random_and_ragged(gpu_ctx, oracle, n):
+def test_fixed_base_random_and_ragged(gpu_ctx, lane_ctx, oracle, n):  # noqa: F811
     from babyjubjub_rs_amd import workload
     sc = workload.random_u256(workload.SEED_SCALARS, n)  # full 256-bit scalars (unreduced)
-    got = gpu_ctx.mul_fixed_base(sc)
-    assert (got == oracle.mul_fixed_base(sc)).all()
+    want = oracle.mul_fixed_base(sc)
+    for ctx, form in both(gpu_ctx, lane_ctx):
+        got = ctx.mul_fixed_base(sc)
+        ran(ctx, "fixed", form)
+        assert (got == want).all(), form
 
 
 def test_empty_batches(gpu_ctx):
@@ -85,7 +99,7 @@ def _points(oracle, golden, n, seed):
     return oracle.point_add(base, tp)
 
 
-def test_var_base_random_full_group(gpu_ctx, oracle, golden):
+def test_var_base_random_full_group(gpu_ctx, lane_ctx, oracle, golden):  # noqa: F811
     from babyjubjub_rs_amd import workload
     n = 1536
     pts = _points(oracle, golden, n, workload.SEED_POINTS)
@@ -93,42 +107,52 @@ def test_var_base_random_full_group(gpu_ctx, oracle, golden):
     # edge rows: identity, order-2 point, off-curve garbage, zero scalar, huge scalars
     pts[0] = pack([(0, 1)]); pts[1] = pack([(0, Q - 1)]); pts[2] = 7; pts[3] = 0
     sc[4] = 0; sc[5] = 255; sc[6] = pack([ORDER]); sc[7] = pack([L])
-    got = gpu_ctx.mul_var_base(pts, sc)
     want = oracle.mul_var_base(pts, sc)
-    bad = np.nonzero((got != want).any(axis=1))[0]
-    assert bad.size == 0, bad[:8]
+    for ctx, form in both(gpu_ctx, lane_ctx):
+        got = ctx.mul_var_base(pts, sc)
+        ran(ctx, "var", form)
+        bad = np.nonzero((got != want).any(axis=1))[0]
+        assert bad.size == 0, (form, bad[:8])
 
 
-def test_poseidon_random(gpu_ctx, oracle):
+def test_poseidon_random(gpu_ctx, lane_ctx, oracle):  # noqa: F811
     from babyjubjub_rs_amd import workload
     n = 4096
     a = workload.random_u256(workload.SEED_MSGS, 5 * n).reshape(n, 160)  # values >= r are reduced on both sides
-    assert (gpu_ctx.poseidon5(a) == oracle.poseidon5(a)).all()
+    want = oracle.poseidon5(a)
+    for ctx, form in both(gpu_ctx, lane_ctx):
+        got = ctx.poseidon5(a)
+        ran(ctx, "poseidon", form)
+        assert (got == want).all(), form
 
 
 from babyjubjub_rs_amd.workload import make_signatures, corrupt  # noqa: E402  (the cfg-4 generator lives with the other workloads)
 
 
-def test_verify_random_with_corruption(gpu_ctx, oracle):
+def test_verify_random_with_corruption(gpu_ctx, lane_ctx, oracle):  # noqa: F811
     n = 2048
     A, R, S, msg = make_signatures(oracle.mul_fixed_base, oracle.poseidon5, n)
     bad = corrupt(A, R, S, msg, n)
     assert bad.sum() > 8
-    got = gpu_ctx.eddsa_verify(A, R, S, msg)
     want = oracle.verify(A, R, S, msg)
-    assert (got == want).all()
-    assert (got[~bad] == 1).all() and (got[bad] == 0).all()
+    for ctx, form in both(gpu_ctx, lane_ctx):
+        got = ctx.eddsa_verify(A, R, S, msg)
+        ran(ctx, "verify", form)
+        assert (got == want).all(), form
+        assert (got[~bad] == 1).all() and (got[bad] == 0).all()
 
 
-def test_verify_msg_range_rule(gpu_ctx, oracle, golden):
+def test_verify_msg_range_rule(gpu_ctx, lane_ctx, oracle, golden):  # noqa: F811
     """msg > Q -> false; msg == Q accepted and hashed as 0 (src/lib.rs:396-399)."""
     from conftest import ints
     c = golden["gpu_expected"]["msg_range_signature"]           # a valid signature of msg = 0 (tests/golden/make_gpu_expected.py)
     A, R, S = ints(c["A"]), ints(c["R"]), ints(c["S"])
     msgs = [0, Q, Q + 1, (1 << 256) - 1, Q - 1]
     n = len(msgs)
-    got = gpu_ctx.eddsa_verify(pack([A] * n), pack([R] * n), pack([S] * n), pack(msgs))
-    assert list(got) == [1, 1, 0, 0, 0]
+    for ctx, form in both(gpu_ctx, lane_ctx):
+        got = ctx.eddsa_verify(pack([A] * n), pack([R] * n), pack([S] * n), pack(msgs))
+        ran(ctx, "verify", form)
+        assert list(got) == [1, 1, 0, 0, 0], form
     assert list(oracle.verify(pack([A] * n), pack([R] * n), pack([S] * n), pack(msgs))) == [1, 1, 0, 0, 0]
 
 
@@ -137,20 +161,24 @@ def test_fixed_base_other_window_widths(oracle, window_bits):
     """the table geometry is a tuning knob; results must not depend on it (13 does not divide 256)."""
     import babyjubjub_rs_amd as bjj
     from babyjubjub_rs_amd import workload
-    ctx = bjj.Context(0, window_bits)
-    try:
-        info = ctx.info()
-        assert info.window_bits == window_bits and info.n_windows == -(-252 // window_bits)
-        assert info.table_bytes == info.n_windows * ((1 << (window_bits - 1)) + 1) * 128
-        assert ctx.check_table() == 0   # every entry, by induction from B8, on the device
-        sc = workload.random_u256(workload.SEED_SCALARS, 777, offset=5)
-        sc[0] = 255
-        assert (ctx.mul_fixed_base(sc) == oracle.mul_fixed_base(sc)).all()
-        A, R, S, msg = make_signatures(oracle.mul_fixed_base, oracle.poseidon5, 130)
-        S[3, 0] ^= 1
-        assert (ctx.eddsa_verify(A, R, S, msg) == oracle.verify(A, R, S, msg)).all()
-    finally:
-        ctx.close()
+    from dispatch_forms import make_lane_ctx
+    for form in (SHORT, LANE):                                  # 777 and 130 items are short calls: both kernels over each table
+        ctx = bjj.Context(0, window_bits) if form == SHORT else make_lane_ctx(window_bits)
+        try:
+            info = ctx.info()
+            assert info.window_bits == window_bits and info.n_windows == -(-252 // window_bits)
+            assert info.table_bytes == info.n_windows * ((1 << (window_bits - 1)) + 1) * 128
+            assert ctx.check_table() == 0   # every entry, by induction from B8, on the device
+            sc = workload.random_u256(workload.SEED_SCALARS, 777, offset=5)
+            sc[0] = 255
+            assert (ctx.mul_fixed_base(sc) == oracle.mul_fixed_base(sc)).all()
+            ran(ctx, "fixed", form)
+            A, R, S, msg = make_signatures(oracle.mul_fixed_base, oracle.poseidon5, 130)
+            S[3, 0] ^= 1
+            assert (ctx.eddsa_verify(A, R, S, msg) == oracle.verify(A, R, S, msg)).all()
+            ran(ctx, "verify", form)
+        finally:
+            ctx.close()
 
 
 def test_fixed_base_table_is_sound_and_signed_digit_edges(gpu_ctx, oracle):
@@ -165,8 +193,14 @@ def test_fixed_base_table_is_sound_and_signed_digit_edges(gpu_ctx, oracle):
              sum(((1 << W) - 1) << (W * j) for j in range(0, nw, 2)), l - half, l + half]
     sc = pack([c % (1 << 256) for c in cases])
     got = gpu_ctx.mul_fixed_base(sc)
+    ran(gpu_ctx, "fixed", SHORT)                                # 19 items: four lanes per item
     assert (got == oracle.mul_fixed_base(sc)).all()
     assert unpack(got[0].tobytes(), 2)[0] == (0, 1) and unpack(got[7].tobytes(), 2)[0] == (0, 1)
+    # the same scalars over the same table on K1, the kernel of the large calls: tiled past the short-call threshold of 2^15 items
+    reps = (1 << 15) // len(cases) + 1
+    tiled = gpu_ctx.mul_fixed_base(np.tile(sc.reshape(-1, 32), (reps, 1)))
+    ran(gpu_ctx, "fixed", LANE)
+    assert (tiled == np.tile(got, (reps, 1))).all()
 
 
 def test_batches_beyond_2_to_the_31_bytes(gpu_ctx, oracle):
@@ -345,7 +379,7 @@ def test_full_size_verify_1m(gpu_ctx, oracle):
     assert (got[idx] == oracle.verify(A[idx], R[idx], S[idx], msg[idx])).all()
 
 
-def test_config0_bench_point_1k_scalars(gpu_ctx, oracle, golden):
+def test_config0_bench_point_1k_scalars(gpu_ctx, lane_ctx, oracle, golden):  # noqa: F811
     """BASELINE.json configs[0]: benches/bench_babyjubjub.rs:15-38 -- mul_scalar on the bench point with
     1 000 random 254-bit scalars (SURVEY.md 8d cfg 1) plus the two literal criterion scalars."""
     from babyjubjub_rs_amd import workload as w
@@ -355,16 +389,21 @@ def test_config0_bench_point_1k_scalars(gpu_ctx, oracle, golden):
     sc = np.concatenate([sc, pack(b["scalars"]).reshape(-1, 32)])
     pts = np.tile(pack([tuple(b["p"])]), (sc.shape[0], 1))
     got = gpu_ctx.mul_var_base(pts, sc)
+    ran(gpu_ctx, "var", SHORT)
     assert (got == oracle.mul_var_base(pts, sc)).all()
+    assert (lane_ctx.mul_var_base(pts, sc) == got).all()        # the same call on K2, the kernel of the large calls
+    ran(lane_ctx, "var", LANE)
     import hashlib
     # the digest is printed so a maintainer can compare runs / boxes; the byte comparison above is the test
     print("cfg0 output sha256:", hashlib.sha256(got.tobytes()).hexdigest())
 
 
-def test_verify_small_order_and_torsion_cases(gpu_ctx, oracle, golden):
+def test_verify_small_order_and_torsion_cases(gpu_ctx, lane_ctx, oracle, golden):  # noqa: F811
     """verdicts that hinge on the cofactor: pk of small order (8*hm*pk vanishes, so s*B8 == R decides),
     R or pk shifted by torsion points, s beyond l.  The GPU path multiplies the check by a short ODD v,
-    which must not change any of these verdicts (verify)."""
+    which must not change any of these verdicts (verify).  96 signatures are a short call: the session's
+    context runs the eight-lanes-per-signature kernel (last_verify_dispatch 2), so the same call goes to a context created with
+    BJJ_VERIFY_SMALL_MAX=0 as well, which runs K4 (0 or 1), the kernel of the large calls; every verdict is asserted for both."""
     from babyjubjub_rs_amd import workload as w
     from conftest import ints
     tors = [ints(t) for t in golden["gpu_expected"]["torsion_points"]]   # the 8 points of order dividing 8 (j * T8)
@@ -385,10 +424,12 @@ def test_verify_small_order_and_torsion_cases(gpu_ctx, oracle, golden):
         else:               # random pk: just compare with the oracle
             pk.append(unpack(sB[(i + 1) % n], 2)[0]); R.append(sb); want_true.append(None)
         S.append(s_int[i])
-    got = gpu_ctx.eddsa_verify(pack(pk), pack(R), pack(S), msg)
     want = oracle.verify(pack(pk), pack(R), pack(S), msg)
-    assert (got == want).all()
-    for i, wt in enumerate(want_true):
-        if wt is not None:
-            assert bool(got[i]) == wt, i
-    assert got.sum() >= n // 3
+    for ctx, form in both(gpu_ctx, lane_ctx):
+        got = ctx.eddsa_verify(pack(pk), pack(R), pack(S), msg)
+        assert ctx.info().last_verify_dispatch == 2 if form == SHORT else ctx.info().last_verify_dispatch in (0, 1), form
+        assert (got == want).all(), form
+        for i, wt in enumerate(want_true):
+            if wt is not None:
+                assert bool(got[i]) == wt, (form, i)
+        assert got.sum() >= n // 3

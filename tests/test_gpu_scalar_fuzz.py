@@ -20,6 +20,7 @@ import pytest
 
 import scalar_ref as sr
 from conftest import ROOT, pack, unpack
+from dispatch_forms import LANE, SHORT, both, lane_ctx, ran  # noqa: F401  (lane_ctx: the fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -154,18 +155,27 @@ def _fixed_base_scalars():
     return sr.edges_mod_l() + [rnd.getrandbits(256) for _ in range(256)]
 
 
-def _check_fixed_base(ctx, oracle, vals, one_item=48):
+def _check_fixed_base(ctx, oracle, vals, one_item=48, forced_k1=False):
+    """the values in one call, which is a short one (four lanes per item) unless the context forces a shape of K1, and tiled
+    past the short-call threshold of 2^15 items, which runs K1 -- both reduce the scalar mod l on their own"""
     sc_ = pack(vals).reshape(-1, 32)
+    assert len(vals) <= 1 << 15
     want = oracle.mul_fixed_base(sc_)
-    got = ctx.mul_fixed_base(sc_)
-    bad = np.nonzero((got != want).any(axis=1))[0]
-    assert bad.size == 0, [vals[i] for i in bad[:4]]
-    comp = ctx.mul_fixed_base_compressed(sc_)
-    bad = np.nonzero((comp != oracle.compress(want)).any(axis=1))[0]
-    assert bad.size == 0, [vals[i] for i in bad[:4]]
+    wantc = oracle.compress(want)
+    reps = (1 << 15) // len(vals) + 1
+    for tile, form in ((1, LANE if forced_k1 else SHORT),) + (() if forced_k1 else ((reps, LANE),)):
+        got = ctx.mul_fixed_base(np.tile(sc_, (tile, 1)))
+        ran(ctx, "fixed", form)
+        bad = np.nonzero((got != np.tile(want, (tile, 1))).any(axis=1))[0]
+        assert bad.size == 0, (form, [vals[i % len(vals)] for i in bad[:4]])
+        comp = ctx.mul_fixed_base_compressed(np.tile(sc_, (tile, 1)))
+        ran(ctx, "fixed", form)
+        bad = np.nonzero((comp != np.tile(wantc, (tile, 1))).any(axis=1))[0]
+        assert bad.size == 0, (form, [vals[i % len(vals)] for i in bad[:4]])
     step = max(1, len(vals) // one_item)
     for i in range(0, len(vals), step):                   # one-item calls: the quad kernel
         assert (ctx.mul_fixed_base(sc_[i:i + 1]) == want[i:i + 1]).all(), vals[i]
+    ran(ctx, "fixed", LANE if forced_k1 else SHORT)
 
 
 def test_abi_fixed_base_mod_l_boundaries(gpu_ctx, ctx_w23, oracle):
@@ -184,7 +194,7 @@ def test_abi_fixed_base_mod_l_boundaries_windows(oracle, monkeypatch, window, k1
         monkeypatch.delenv("BJJ_K1_VARIANT")
     try:
         assert ctx.info().window_bits == window
-        _check_fixed_base(ctx, oracle, _fixed_base_scalars(), one_item=16)
+        _check_fixed_base(ctx, oracle, _fixed_base_scalars(), one_item=16, forced_k1=k1 is not None)
     finally:
         ctx.close()
 
@@ -205,21 +215,26 @@ def _eddsa_cases(oracle, nsig):
     return A[idx], R[idx], pack([v for _, v in rows]).reshape(-1, 32), msg[idx], np.array(want, np.uint8)
 
 
-def test_abi_eddsa_verify_s_plus_multiples_of_l(gpu_ctx, oracle, sc):
+def test_abi_eddsa_verify_s_plus_multiples_of_l(gpu_ctx, lane_ctx, oracle, sc):  # noqa: F811
     _require_exact_euclid(sc)                                                     # the EdDSA fast path runs lattice_short_pair
     A, R, S, msg, want = _eddsa_cases(oracle, 12)
     assert (oracle.verify(A, R, S, msg) == want).all()
-    assert (gpu_ctx.eddsa_verify(A, R, S, msg) == want).all()                      # one long batch
+    assert len(want) <= 1 << 13                   # a short call all the same: eight lanes per signature; then K4 on the same batch
+    for ctx, form in both(gpu_ctx, lane_ctx):
+        assert (ctx.eddsa_verify(A, R, S, msg) == want).all(), form               # one long batch
+        ran(ctx, "verify", form)
     for i in range(0, len(want), 37):                                             # short calls
         assert (gpu_ctx.eddsa_verify(A[i:i + 5], R[i:i + 5], S[i:i + 5], msg[i:i + 5]) == want[i:i + 5]).all(), i
     # the wire format: compressed pk, compressed R || s
     pkc, rc = oracle.compress(A), oracle.compress(R)
     sig = np.concatenate([rc, S], axis=1)
     assert (oracle.verify_compressed(pkc, sig, msg) == want).all()
-    assert (gpu_ctx.eddsa_verify_compressed(pkc, sig, msg) == want).all()
+    for ctx, form in both(gpu_ctx, lane_ctx):
+        assert (ctx.eddsa_verify_compressed(pkc, sig, msg) == want).all(), form
+        ran(ctx, "verify", form)
 
 
-def test_abi_schnorr_verify_s_plus_multiples_of_l(gpu_ctx, oracle):
+def test_abi_schnorr_verify_s_plus_multiples_of_l(gpu_ctx, lane_ctx, oracle):  # noqa: F811
     rng = np.random.default_rng(0x5CA1)
     n = 8
     keys = rng.integers(0, 256, (n, 32), dtype=np.uint8)
@@ -228,6 +243,9 @@ def test_abi_schnorr_verify_s_plus_multiples_of_l(gpu_ctx, oracle):
     r, s, ok = gpu_ctx.sign_schnorr(keys, msgs, nonces)
     assert ok.all()
     pk = gpu_ctx.public_keys(keys)
+    ran(gpu_ctx, "fixed", SHORT)
+    assert (lane_ctx.public_keys(keys) == pk).all()
+    ran(lane_ctx, "fixed", LANE)
     rows, want = [], []
     for i in range(n):
         sl = int.from_bytes(s[i].tobytes(), "little") % L
@@ -240,7 +258,9 @@ def test_abi_schnorr_verify_s_plus_multiples_of_l(gpu_ctx, oracle):
     idx = np.array([i for i, _ in rows])
     sv, want = pack([v for _, v in rows]).reshape(-1, 32), np.array(want, np.uint8)
     assert (oracle.verify_schnorr(pk[idx], r[idx], sv, msgs[idx]) == want).all()
-    assert (gpu_ctx.schnorr_verify(pk[idx], r[idx], sv, msgs[idx]) == want).all()
+    for ctx, form in both(gpu_ctx, lane_ctx):     # about a thousand signatures: a short call, and K4 on the same batch
+        assert (ctx.schnorr_verify(pk[idx], r[idx], sv, msgs[idx]) == want).all(), form
+        ran(ctx, "verify", form)
 
 
 def _group_points(ctx, n, seed):
@@ -248,7 +268,7 @@ def _group_points(ctx, n, seed):
     return ctx.mul_fixed_base(w.scalars_254(n, offset=seed)).copy()
 
 
-def test_abi_var_base_k_plus_multiples_of_8l(gpu_ctx, oracle):
+def test_abi_var_base_k_plus_multiples_of_8l(gpu_ctx, lane_ctx, oracle):  # noqa: F811
     """for on-curve points n*P == (n mod 8l)*P: k + q 8l gives k's result, in short calls, in one batch and in bjj_msm"""
     rnd = random.Random(0x88)
     m = 16
@@ -258,8 +278,10 @@ def test_abi_var_base_k_plus_multiples_of_8l(gpu_ctx, oracle):
     rows = [(i, k + q * ORDER) for i, k in enumerate(ks) for q in range(6) if k + q * ORDER < 1 << 256]
     idx = np.array([i for i, _ in rows])
     big = pack([v for _, v in rows]).reshape(-1, 32)
-    got = gpu_ctx.mul_var_base(pts[idx], big)
-    assert (got == want[idx]).all()
+    for ctx, form in both(gpu_ctx, lane_ctx):     # four lanes per item and K2: each reduces the scalar mod 8l on its own
+        got = ctx.mul_var_base(pts[idx], big)
+        ran(ctx, "var", form)
+        assert (got == want[idx]).all(), form
     for j in range(0, len(rows), 5):                                                # short calls (quad kernel)
         assert (gpu_ctx.mul_var_base(pts[idx[j:j + 3]], big[j:j + 3]) == want[idx[j:j + 3]]).all(), rows[j]
     # msm: the same sum with every scalar replaced by k + q 8l (the largest q that fits)
@@ -273,17 +295,20 @@ def test_abi_var_base_k_plus_multiples_of_8l(gpu_ctx, oracle):
         assert (gpu_ctx.msm(pts, pack(kq).reshape(-1, 32)) == acc).all(), q
 
 
-def test_abi_var_base_wide_every_word_count(gpu_ctx, oracle):
+def test_abi_var_base_wide_every_word_count(gpu_ctx, lane_ctx, oracle):  # noqa: F811
     """bjj_mul_var_base_wide on the wide edge set, every scalar_bytes, against the oracle at n mod 8l"""
     pts_all = _group_points(gpu_ctx, 64, 0x71DE)
     for nw in sr.WIDE_WORD_COUNTS:
         vals = sr.edges_wide(nw)
         pts = pts_all[np.arange(len(vals)) % 64]
         scal = sr.words(vals, nw).view(np.uint8).reshape(len(vals), 4 * nw)
-        got = gpu_ctx.mul_var_base_wide(pts, scal, 4 * nw)
         want = oracle.mul_var_base(pts, pack([v % ORDER for v in vals]).reshape(-1, 32))
-        bad = np.nonzero((got != want).any(axis=1))[0]
-        assert bad.size == 0, (nw, [hex(vals[i]) for i in bad[:3]])
+        # 32-byte scalars in a short call run four lanes per item: those go to K2 as well; wider ones run K2 at every size
+        for ctx, form in ((gpu_ctx, SHORT if nw == 8 else LANE),) + (((lane_ctx, LANE),) if nw == 8 else ()):
+            got = ctx.mul_var_base_wide(pts, scal, 4 * nw)
+            ran(ctx, "var", form)
+            bad = np.nonzero((got != want).any(axis=1))[0]
+            assert bad.size == 0, (nw, form, [hex(vals[i]) for i in bad[:3]])
 
 
 SCHNORR_NONCES_ELSEWHERE = {0, 1, L - 1, L, (1 << 261) - 1, 1 << 1023, (1 << 1024) - 1}   # tests/test_schnorr.py signs these
