@@ -77,6 +77,52 @@ BJJ_HD Ext ext_madd(const Ext& p, const Niels& q) {
   if (NEED_T) r.T = fr_mul(e, h); else r.T = fr_zero();
   return r;
 }
+// ext_madd with the accumulator kept between two additions as the addition first forms it: Y - X, Y + X and 2Z (lazy) and T
+// (K1's overlap form, k_fixed.hip: K1Acc; the host model tests/emul/k1_sign_carry_main.cpp runs these very functions).
+// Operand bounds: ym < 6r with limbs < 1.5 * 2^30, yp < 4r and d < 4r with limbs < 2^30, T N-form or a lazy negation (limbs
+// < 2^30, < 4r); the entry N-form < 2r but for t2d, which may be a lazy negation when T is not.
+// `flip` returns the NEGATED sum: -(X, Y, Z, T) = (-X, Y, Z, -T), and X = e f, T = e h share the factor e = b - a, so the
+// negation is e = a - b: one select between two lazy differences of the same two N-form products, the bounds are e's own.
+struct MaddState { Fr ym, yp, d, T; };
+template <bool NEED_T = true>
+BJJ_HD Ext ext_madd_state(const MaddState& s, const Niels& q, bool flip = false) {
+  Fr a = fr_mul(s.ym, q.ymx);
+  Fr b = fr_mul(s.yp, q.ypx);
+  Fr c = fr_mul(s.T, q.t2d);
+  Fr h = fr_add_lazy(b, a);                      // < 4r,  limbs < 2^30
+  // e = fr_sub_lazy(x, y) with (x, y) = flip ? (a, b) : (b, a), limb for limb: y = h - x, so x + 4r - y = 2x + 4r - h -- one
+  // select, one shift-add and one subtraction per limb
+  Fr e;                                          // < 6r,  limbs < 1.5*2^30
+#pragma unroll
+  for (int i = 0; i < NL; i++) {
+    const u32 x = flip ? a.v[i] : b.v[i];
+    BJJ_ASSERT(h.v[i] - x <= fr_c4limb(i));
+    e.v[i] = (x << 1) + fr_c4limb(i) - h.v[i];
+  }
+  Fr f = fr_sub(s.d, c);                         // < 8r,  carried
+  Fr g = fr_add_lazy(s.d, c);                    // < 6r,  limbs < 1.5*2^30
+  Ext r;
+  r.X = fr_mul(e, f); r.Y = fr_mul(g, h); r.Z = fr_mul(f, g);
+  if (NEED_T) r.T = fr_mul(e, h); else r.T = fr_zero();
+  return r;
+}
+BJJ_HD MaddState ext_madd_forms(const Ext& p) {   // p's coordinates N-form < 2r (products)
+  MaddState s;
+  s.ym = fr_sub_lazy(p.Y, p.X); s.yp = fr_add_lazy(p.Y, p.X); s.d = fr_add_lazy(p.Z, p.Z); s.T = p.T;
+  return s;
+}
+// A T-form entry (x', y) of window 0 (bjj_device.hpp "fixed base") IS such a state: Y - X = 2(y - x'), Y + X = 2(y + x'), 2Z = 4,
+// T = 2x'y of the point (2x' : 2y : 2 : 2x'y).  `neg`: the state of -(x', y) in Y - X and Y + X (they swap); T is left to the
+// caller, who negates it (`neg_t`, lazily) or moves its sign into the next entry's t2d.
+BJJ_HD MaddState niels_tform_state(const Niels& e0, bool neg, bool neg_t) {
+  MaddState s;
+  const Fr ymx = fr_select(neg, e0.ypx, e0.ymx), ypx = fr_select(neg, e0.ymx, e0.ypx);
+  s.ym = fr_add_lazy(ymx, ymx);                  // twice an N-form entry < 2r: lazy sums, limbs < 2^30, < 4r
+  s.yp = fr_add_lazy(ypx, ypx);
+  s.d = fr_add(fr_add(fr_one(), fr_one()), fr_add(fr_one(), fr_one()));   // the constant 4: N-form, < 4r
+  s.T = fr_select(neg_t, fr_sub_lazy(fr_zero(), e0.t2d), e0.t2d);          // N-form as stored, or limbs < 2^30, < 4r
+  return s;
+}
 // P + Q, Q projective-precomputed (entries carried).  8M; 7M when the caller does not need T (need_t is wave-uniform in
 // the kernels: a doubling follows, which never reads T).
 BJJ_HD Ext ext_add_pn(const Ext& p, const PNiels& q, bool need_t = true) {

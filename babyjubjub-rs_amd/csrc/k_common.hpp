@@ -184,6 +184,14 @@ __device__ __forceinline__ void epilogue_run(Fr run, size_t n, size_t tid, size_
 // of which lane L moves a chunk each, are the eight consecutive words from (L / 8) * 8.  The strip is rewritten by every
 // gather; a wave's LDS operations complete in the order they were issued, so the reads of the gather before are done when
 // the write lands, and the reads below follow the write: the compiler's own lgkmcnt waits order the rest.  No barrier.
+// BJJ_K1_ADDR_MAD (the STRIP instantiation only): a load's address slot * 128 + (table + 16 c) is ONE v_mad_u64_u32 per load.
+// The compiler forms it with a 64-bit shift and a 64-bit add, two quarter-rate instructions (a shift by 7 does not fit the
+// fused shift-add).  The chunk c = (L & 7) ^ ((e >> 1) & 7) of entry e = 8k + L / 8 is (L & 7) ^ (L >> 4) for even k and that
+// value ^ 4 for odd k ((e >> 1) & 7 = (4k + (L >> 4)) & 7 and L >> 4 < 4), so two per-lane 64-bit bases serve the eight loads.
+// One asm statement: every statement costs a padding s_nop (fr.hpp).
+#ifndef BJJ_K1_ADDR_MAD
+#define BJJ_K1_ADDR_MAD 1
+#endif
 #define FB_STRIP_WORDS 64
 template <int NBUF, bool STRIP = false>
 struct GatherCoopLds {
@@ -207,6 +215,27 @@ struct GatherCoopLds {
   __device__ __forceinline__ void issue(size_t slot, Pending&, int buf) const {
     u32 ss[8];
     if (STRIP) strip_slots((u32)slot, ss);
+#if BJJ_K1_ADDR_MAD
+    if constexpr (STRIP) {
+      const u32 c0 = (u32)((lane & 7) ^ (lane >> 4));
+      const u64 b0 = (u64)(uintptr_t)table + c0 * 16u, b1 = (u64)(uintptr_t)table + (c0 ^ 4u) * 16u;
+      u64 a[8];
+      asm("v_mad_u64_u32 %0, vcc, %8, %16, %17\n\tv_mad_u64_u32 %1, vcc, %9, %16, %18\n\t"
+          "v_mad_u64_u32 %2, vcc, %10, %16, %17\n\tv_mad_u64_u32 %3, vcc, %11, %16, %18\n\t"
+          "v_mad_u64_u32 %4, vcc, %12, %16, %17\n\tv_mad_u64_u32 %5, vcc, %13, %16, %18\n\t"
+          "v_mad_u64_u32 %6, vcc, %14, %16, %17\n\tv_mad_u64_u32 %7, vcc, %15, %16, %18"
+          : "=&v"(a[0]), "=&v"(a[1]), "=&v"(a[2]), "=&v"(a[3]), "=&v"(a[4]), "=&v"(a[5]), "=&v"(a[6]), "=&v"(a[7])
+          : "v"(ss[0]), "v"(ss[1]), "v"(ss[2]), "v"(ss[3]), "v"(ss[4]), "v"(ss[5]), "v"(ss[6]), "v"(ss[7]),
+            "s"(NIELS_WORDS * 4u), "v"(b0), "v"(b1)
+          : "vcc");
+#pragma unroll
+      for (int k = 0; k < 8; k++)
+        __builtin_amdgcn_global_load_lds((const u32*)(uintptr_t)a[k],
+                                         (__attribute__((address_space(3))) void*)(wlds + (NBUF > 1 ? buf : 0) * FB_STAGE_WORDS + k * (8 * NIELS_WORDS)),
+                                         16, 0, NBUF > 1 ? BJJ_GATHER_AUX : BJJ_GATHER_AUX_NBUF1);
+      return;
+    }
+#endif
 #pragma unroll
     for (int k = 0; k < 8; k++) {
       const int e = 8 * k + (lane >> 3);

@@ -55,6 +55,31 @@
 #ifndef BJJ_K1_SLOT_STRIP
 #define BJJ_K1_SLOT_STRIP 1
 #endif
+// Glue instructions of the overlap form that the result does not need; each part has its own A/B knob (DESIGN.md section 6,
+// profiles/r12_ab_k1_glue.txt):
+//   BJJ_K1_SIGN_CARRY   the accumulator carries the sign of the current digit, so a table entry is used as it leaves LDS: no
+//                       swap of y - x' / y + x' and no negated 2D'x'y per window (the comment above K1Acc); needs BJJ_K1_FOLD_LIFT
+//   BJJ_K1_REG_RECORDS  phase 2 has its own loop (k1_epilogue_run) and takes the four values of a record apart, and its results
+//                       together, in registers: through an array of eight words the compiler routes them through LDS
+//   BJJ_K1_ADDR_MAD     k_common.hpp: one multiply-add per address of the gather
+#ifndef BJJ_K1_SIGN_CARRY
+#define BJJ_K1_SIGN_CARRY 1
+#endif
+#ifndef BJJ_K1_REG_RECORDS
+#define BJJ_K1_REG_RECORDS 1
+#endif
+//   BJJ_K1_UNIFORM_STAGE the wave's staging area is addressed from the wave index as a scalar (one v_readfirstlane_b32 per launch):
+//                       the LDS base of each of a gather's eight loads, which goes to M0, was a vector add and a
+//                       v_readfirstlane_b32 per load
+//   BJJ_K1_ALIGN_DIGITS the digit stream moves down by one v_alignbit_b32 per word (k1_digit_next); for a run-time width the
+//                       compiler forms digit_next's funnel shift from a shift and a shift-or
+#ifndef BJJ_K1_UNIFORM_STAGE
+#define BJJ_K1_UNIFORM_STAGE 1
+#endif
+#ifndef BJJ_K1_ALIGN_DIGITS
+#define BJJ_K1_ALIGN_DIGITS 1
+#endif
+#define K1_SIGN_CARRY (BJJ_K1_SIGN_CARRY && BJJ_K1_FOLD_LIFT)   // it works on the folded state: off without it
 
 // ---------------------------------------------------------------------------
 // init: fixed-base table (layout and recoding: bjj_device.hpp "fixed base").
@@ -112,6 +137,20 @@ __device__ __forceinline__ Fr k1_scalar_limbs(const U4 (&v)[2]) {
   s.v[8] = v[1].w >> 8;
   return s;
 }
+// digit_next (bjj_device.hpp) with the shift register moved by funnel shifts: the same digits, slots and carries
+__device__ __forceinline__ size_t k1_digit_next(DigitStream& d, bool& neg) {
+  if (!BJJ_K1_ALIGN_DIGITS) return digit_next(d, neg);
+  const u32 u = (d.w[0] & d.mask) + d.carry;
+  neg = u > d.half;
+  d.carry = neg ? 1u : 0u;
+  const u32 dig = neg ? (d.mask + 1u) - u : u;
+  const size_t slot = d.base + dig;
+  d.base += d.stride;
+#pragma unroll
+  for (int i = 0; i < 7; i++) d.w[i] = __builtin_amdgcn_alignbit(d.w[i + 1], d.w[i], (u32)d.W);   // 4 <= W <= 28
+  d.w[7] >>= d.W;
+  return slot;
+}
 template <class G>
 __device__ __forceinline__ K1Item k1_item_begin(const G& g, int W, const U4 (&scalar)[2]) {
   u32 sc[8];
@@ -121,48 +160,58 @@ __device__ __forceinline__ K1Item k1_item_begin(const G& g, int W, const U4 (&sc
   K1Item it;
   it.ds = digit_stream(sc, W);
   typename G::Pending p;
-  g.issue(digit_next(it.ds, it.neg0), p, 0);
-  g.issue(digit_next(it.ds, it.neg1), p, 1);
+  g.issue(k1_digit_next(it.ds, it.neg0), p, 0);
+  g.issue(k1_digit_next(it.ds, it.neg1), p, 1);
   return it;
 }
 #if BJJ_K1_FOLD_LIFT
 // The accumulator between two additions as ext_madd first forms it: Y - X, Y + X and 2Z (lazy) and T.  Kept in this shape the
 // window loop stays rolled, does per trip exactly what ext_madd does, and window 0's entry (x', y) -- in T form -- IS a
 // state: Y - X = 2(y - x'), Y + X = 2(y + x'), 2Z = 4, T = 2x'y of the point (2x' : 2y : 2 : 2x'y) that fixed_base_mul lifts it to.
-struct K1Acc { Fr ym, yp, d, T; };
+//
+// BJJ_K1_SIGN_CARRY.  Let eps_j = +-1 be the sign of window j's digit, Q_j its entry as stored, S_j = sum_{i <= j} eps_i Q_i the
+// partial sum fixed_base_mul holds after window j.  The loop holds R_j = eps_j S_j instead:
+//     R_0 = Q_0,      R_j = (eps_j eps_{j-1}) R_{j-1} + Q_j,      result S_last = eps_last R_last = R_last,
+// so an addition takes its entry exactly as the gather returns it, and what is negated -- when two neighbouring digits differ in
+// sign -- is the accumulator.  That costs nothing where the accumulator is made: -(X, Y, Z, T) = (-X, Y, Z, -T), and in the
+// addition X = e f and T = e h share the factor e = b - a, so addition j-1 forms e as b - a or a - b by ONE select on
+// eps_j eps_{j-1} (`flip`; the digit of window j is drawn before addition j-1 runs, for its gather).  The last addition does not
+// flip: eps_last = +1 always, because the reduced scalar is not negative -- a negative top digit would leave a carry behind the
+// top window, which scalar_mod_l_weak's contract excludes for every width (bjj_device.hpp; tests/test_k1_weak_mod_l_host.py) --
+// so R_last is S itself.  Window 0 has no addition before it: its state swaps Y - X / Y + X and
+// negates T (lazily) by eps_0 eps_1, which are the selects and the negation it had for eps_0 and for window 1's t2d.
+// Bounds: a and b are N-form products < 2r, and fr_sub_lazy is the same function of either order, so e keeps < 6r with limbs
+// < 1.5 * 2^30 and every other operand is untouched; the entry's t2d is now always N-form < 2r, and the one lazy negation left,
+// window 0's T (limbs < 2^30, < 4r), meets that N-form t2d in c = T * t2d, the mirror image of the pair it replaces.
+// Per window: 18 selects and 9 subtractions plus 9 selects on the entry go, 9 subtractions and 9 selects on e come.
+// The functions are curve.hpp's (MaddState), which the host model tests/emul/k1_sign_carry_main.cpp runs as well.
+typedef MaddState K1Acc;
 // ext_madd on that state.  Operand bounds as in curve.hpp: ym < 6r with limbs < 1.5 * 2^30, yp < 4r and d < 4r with limbs
 // < 2^30, T N-form; the entry N-form < 2r but for t2d, which may be a lazy negation (limbs < 2^30, < 4r).
 template <bool NEED_T = true>
-__device__ __forceinline__ Ext k1_madd(const K1Acc& s, const Niels& q) {
-  Fr a = fr_mul(s.ym, q.ymx);
-  Fr b = fr_mul(s.yp, q.ypx);
-  Fr c = fr_mul(s.T, q.t2d);
-  Fr e = fr_sub_lazy(b, a);                      // < 6r,  limbs < 1.5*2^30
-  Fr f = fr_sub(s.d, c);                         // < 8r,  carried
-  Fr g = fr_add_lazy(s.d, c);                    // < 6r,  limbs < 1.5*2^30
-  Fr h = fr_add_lazy(b, a);                      // < 4r,  limbs < 2^30
-  Ext r;
-  r.X = fr_mul(e, f); r.Y = fr_mul(g, h); r.Z = fr_mul(f, g);
-  if (NEED_T) r.T = fr_mul(e, h); else r.T = fr_zero();
-  return r;
+__device__ __forceinline__ Ext k1_madd(const K1Acc& s, const Niels& q, bool flip = false) {
+  return ext_madd_state<NEED_T>(s, q, K1_SIGN_CARRY && flip);
 }
-__device__ __forceinline__ K1Acc k1_forms(const Ext& p) {   // p's coordinates N-form < 2r (products)
-  K1Acc s;
-  s.ym = fr_sub_lazy(p.Y, p.X); s.yp = fr_add_lazy(p.Y, p.X); s.d = fr_add_lazy(p.Z, p.Z); s.T = p.T;
-  return s;
-}
+__device__ __forceinline__ K1Acc k1_forms(const Ext& p) { return ext_madd_forms(p); }
 #else
 typedef Ext K1Acc;
 template <bool NEED_T = true>
-__device__ __forceinline__ Ext k1_madd(const K1Acc& s, const Niels& q) { return ext_madd<NEED_T>(s, q); }
+__device__ __forceinline__ Ext k1_madd(const K1Acc& s, const Niels& q, bool = false) { return ext_madd<NEED_T>(s, q); }
 __device__ __forceinline__ K1Acc k1_forms(const Ext& p) { return p; }
 #endif
+// the entry of a window as the additions take it: as stored, or negated by its digit's sign
+__device__ __forceinline__ Niels k1_entry(const Niels& e, bool neg) { return K1_SIGN_CARRY ? e : niels_cneg_lazy(e, neg); }
 // `mid` runs once both staged entries are in registers: the place for memory traffic that the two waits must not cover.
 template <class G, class MID>
 __device__ __forceinline__ void k1_item_windows(const G& g, int nwin, K1Item& it, K1Acc& acc, Niels& cur, const MID& mid) {
   typename G::Pending p;
-  bool neg;
-#if BJJ_K1_FOLD_LIFT
+  bool neg, last = false;   // BJJ_K1_SIGN_CARRY: the sign of the digit before
+#if K1_SIGN_CARRY
+  acc = niels_tform_state(g.finish(p, 0), it.neg0 != it.neg1, it.neg0 != it.neg1);   // (eps_0 eps_1) Q_0
+  BJJ_SCHED_FENCE();
+  cur = g.finish(p, 1);
+  last = it.neg1;
+#elif BJJ_K1_FOLD_LIFT
   const Niels e0 = g.finish(p, 0);
   const Fr ymx0 = fr_select(it.neg0, e0.ypx, e0.ymx), ypx0 = fr_select(it.neg0, e0.ymx, e0.ypx);
   acc.ym = fr_add_lazy(ymx0, ymx0);              // twice an N-form entry < 2r: lazy sums, limbs < 2^30, < 4r
@@ -184,15 +233,24 @@ __device__ __forceinline__ void k1_item_windows(const G& g, int nwin, K1Item& it
   mid();
 #pragma unroll 1
   for (int j = 1; j + 1 < nwin; j++) {
-    g.issue(digit_next(it.ds, neg), p, (j + 1) & 1);
-    acc = k1_forms(k1_madd(acc, cur));
+    g.issue(k1_digit_next(it.ds, neg), p, (j + 1) & 1);
+    acc = k1_forms(k1_madd(acc, cur, neg != last));   // window j's addition, negated where window j + 1 changes the sign
+    if (K1_SIGN_CARRY) last = neg;
     BJJ_SCHED_FENCE();
-    cur = niels_cneg_lazy(g.finish(p, (j + 1) & 1), neg);
+    cur = k1_entry(g.finish(p, (j + 1) & 1), neg);
   }
 }
 // epilogue_stash (k_common.hpp) in two halves: the four packed values of an item wait in registers until its stores may go.
 struct K1Stash { U4 x[2], y[2], z[2], p[2]; };
+// BJJ_K1_REG_RECORDS: fr_to_words into two vectors, word by word from the limbs (word j starts 32 j - 29 floor(32 j / 29) bits into
+// limb floor(32 j / 29) and ends in the next one), as k1_scalar_limbs does the other way: no array of eight words.
+__device__ __forceinline__ void k1_words(U4 (&v)[2], const Fr& f) {
+  const u32* a = f.v;
+  v[0] = U4{a[0] | (a[1] << 29), (a[1] >> 3) | (a[2] << 26), (a[2] >> 6) | (a[3] << 23), (a[3] >> 9) | (a[4] << 20)};
+  v[1] = U4{(a[4] >> 12) | (a[5] << 17), (a[5] >> 15) | (a[6] << 14), (a[6] >> 18) | (a[7] << 11), (a[7] >> 21) | (a[8] << 8)};
+}
 __device__ __forceinline__ void k1_stash_words(U4 (&v)[2], const Fr& f) {
+  if (BJJ_K1_REG_RECORDS) { k1_words(v, f); return; }
   u32 w[8];
   fr_to_words(f, w);
   v[0] = U4{w[0], w[1], w[2], w[3]}; v[1] = U4{w[4], w[5], w[6], w[7]};
@@ -217,6 +275,7 @@ __device__ __forceinline__ void k1_record_load(K1Record& r, const uint8_t* xy_it
   r.x[0] = q[0]; r.x[1] = q[1]; r.y[0] = q[2]; r.y[1] = q[3];
 }
 __device__ __forceinline__ Fr k1_record_fr(const U4 (&v)[2]) {
+  if (BJJ_K1_REG_RECORDS) return k1_scalar_limbs(v);
   const u32 w[8] = {v[0].x, v[0].y, v[0].z, v[0].w, v[1].x, v[1].y, v[1].z, v[1].w};
   return fr_from_words(w);
 }
@@ -229,6 +288,18 @@ __device__ __forceinline__ void k1_record_finish(Fr& inv, uint8_t* out_item, con
   Fr c2 = fr_mul(zinv, c_K.FINV);         // plain 1/(Z F)
   Fr x = fr_cond_sub_kr(fr_mul(X, c2), R1);
   Fr y = fr_cond_sub_kr(fr_mul(Y, zinv), R1);
+  if (BJJ_K1_REG_RECORDS) {
+    U4 *const o = (U4*)out_item, v[2];
+    if (FORM & EPI_COMPRESS) {
+      k1_words(v, y);
+      if (plain_gt_halfq(x, c_K)) v[1].w |= 0x80000000u;
+      o[0] = v[0]; o[1] = v[1];
+    } else {
+      k1_words(v, x); o[0] = v[0]; o[1] = v[1];
+      k1_words(v, y); o[2] = v[0]; o[3] = v[1];
+    }
+    return;
+  }
   u32 w[8];
   if (FORM & EPI_COMPRESS) {
     fr_to_words(y, w);
@@ -288,7 +359,9 @@ __device__ __forceinline__ void mul_fixed_base_body(const u32* __restrict__ tabl
   const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t nthreads = (size_t)gridDim.x * blockDim.x;
   const int lane = threadIdx.x & 63;
-  const GatherCoopLds<NBUF, STRIP> fb = {table, stage + (threadIdx.x >> 6) * WAVE_WORDS, lane};
+  // the wave index as the compiler can see it is uniform (BJJ_K1_UNIFORM_STAGE; the overlap form only)
+  const int wave = AHEAD && BJJ_K1_UNIFORM_STAGE ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : (int)(threadIdx.x >> 6);
+  const GatherCoopLds<NBUF, STRIP> fb = {table, stage + wave * WAVE_WORDS, lane};
   uint8_t* const stash = (FORM & EPI_COMPRESS) ? xy : out;
   Fr run = fr_one();
   if (AHEAD && BJJ_K1_PIPE_ITEM) {
@@ -324,7 +397,10 @@ __device__ __forceinline__ void mul_fixed_base_body(const u32* __restrict__ tabl
         // back; a lane's last item has no wait behind it to hide under and is stored at once
         pending = BJJ_K1_LATE_SCALAR && more;
         if (pending) { k1_stash_pack(held, p, run); iheld = i; }
-        else if (i < n) epilogue_stash(p, run, stash + i * 64, scratch + i * 16);
+        else if (i < n) {
+          if (BJJ_K1_REG_RECORDS) { k1_stash_pack(held, p, run); k1_stash_store(held, stash + i * 64, scratch + i * 16); }
+          else epilogue_stash(p, run, stash + i * 64, scratch + i * 16);
+        }
         if (!more) break;
         i = inext;
       }
@@ -339,7 +415,7 @@ __device__ __forceinline__ void mul_fixed_base_body(const u32* __restrict__ tabl
       if (valid) epilogue_stash(p, run, stash + i * 64, scratch + i * 16);
     }
   }
-  if (AHEAD && (BJJ_K1_PIPE_RECORD || BJJ_K1_EARLY_RECORD))
+  if (AHEAD && (BJJ_K1_REG_RECORDS || BJJ_K1_PIPE_RECORD || BJJ_K1_EARLY_RECORD))
     k1_epilogue_run<BLOCK, FORM>(run, n, tid, nthreads, out, stash, scratch, lds);
   else
     epilogue_run<BLOCK, FORM, BJJ_K1_INV_CORE>(run, n, tid, nthreads, out, scratch, lds, xy);
