@@ -68,6 +68,9 @@ POINT_SUM_SYMBOLS = ("bjj_point_sum", "bjj_point_sum_dev")
 COMMON_SYMBOLS = ("bjj_mul_common", "bjj_mul_common_dev", "bjj_in_subgroup", "bjj_in_subgroup_dev", "bjj_elgamal_decrypt",
                   "bjj_elgamal_decrypt_dev")
 BJJ_COMMON_OK, BJJ_COMMON_OFF_CURVE = 1, 2
+# ... and include/bjj_hip_elgamal.h
+ELGAMAL_SYMBOLS = ("bjj_elgamal_encrypt", "bjj_elgamal_encrypt_dev")
+BJJ_ELGAMAL_OK, BJJ_ELGAMAL_OFF_CURVE = 1, 2
 
 
 class BjjInfo(ctypes.Structure):
@@ -237,6 +240,8 @@ def load():
     lib.bjj_in_subgroup_dev.argtypes = [vp, vp, sz, vp, vp]
     lib.bjj_elgamal_decrypt.argtypes = [vp, vp, vp, vp, vp, sz, ci, vp, vp]
     lib.bjj_elgamal_decrypt_dev.argtypes = [vp, vp, vp, vp, vp, sz, ci, vp, vp, vp]
+    lib.bjj_elgamal_encrypt.argtypes = [vp, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp]
+    lib.bjj_elgamal_encrypt_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp]
     # multi-GPU
     pd = ctypes.POINTER(ctypes.c_double)
     lib.bjj_multi_init.argtypes = [ctypes.POINTER(ci), ci, ci, ctypes.POINTER(vp)]

@@ -614,6 +614,55 @@ class Context:
         self._ck(self.lib.bjj_elgamal_decrypt_dev(self.handle, self._dlog_handle(table, "decrypt_dev"), k.ctypes.data, d_c1, d_c2, n,
                                                   int(range_bits), d_out_m, d_ok, stream), "bjj_elgamal_decrypt_dev")
 
+    # ---- encryption and re-randomisation in one launch (include/bjj_hip_elgamal.h) ----
+    def _elgamal_handles(self, g, pk, what):
+        for b, name in ((g, "g"), (pk, "pk")):
+            if b is None and name == "g":
+                continue
+            if not isinstance(b, FixedBase) or b.ctx is not self or not b.handle:
+                raise BjjError("%s: %s is a live FixedBase of this context%s" % (what, name, ", or None for B8" if name == "g" else ""))
+        return (None if g is None else g.handle.value), pk.handle.value
+
+    def elgamal_encrypt(self, pk, m, r, g=None, add=None):
+        """exponential ElGamal to the key whose table `pk` is (a FixedBase): c1[i] = r[i] * G, c2[i] = m[i] * G + r[i] * PK in ONE
+        launch (bjj_elgamal_encrypt) -> (c1, c2), (n, 64) uint8 each.  m: n integers below 2^64 (or a uint64 array), None = all 0;
+        r: n 32-byte records (or ints); g: the FixedBase of G, None = B8.  add=(a1, a2): c1[i] = a1[i] + .., c2[i] = a2[i] + .. and
+        -> (c1, c2, ok) with ok 1 = computed, 2 = a1[i] or a2[i] is not on the curve and both outputs are (0, 0).  Byte for byte
+        the composition of mul_bases and point_add.  Not constant time."""
+        hg, hpk = self._elgamal_handles(g, pk, "elgamal_encrypt")
+        rr = _as_u8(r, 32, "r")
+        n = rr.size // 32
+        mm = None
+        if m is not None:
+            mm = np.ascontiguousarray(m if isinstance(m, np.ndarray) and m.dtype == np.uint64 else np.array([int(x) for x in m], dtype=np.uint64))
+            if mm.size != n:
+                raise BjjError("elgamal_encrypt: array lengths disagree")
+        a1 = a2 = None
+        if add is not None:
+            a1, a2 = _as_u8(add[0], 64, "add c1"), _as_u8(add[1], 64, "add c2")
+            if a1.size != n * 64 or a2.size != n * 64:
+                raise BjjError("elgamal_encrypt: array lengths disagree")
+        c1, c2 = np.empty(n * 64, dtype=np.uint8), np.empty(n * 64, dtype=np.uint8)
+        ok = np.empty(n, dtype=np.uint8)
+        self._ck(self.lib.bjj_elgamal_encrypt(self.handle, hg, hpk, None if mm is None else mm.ctypes.data, rr.ctypes.data,
+                                              None if a1 is None else a1.ctypes.data, None if a2 is None else a2.ctypes.data, n,
+                                              c1.ctypes.data, c2.ctypes.data, ok.ctypes.data), "bjj_elgamal_encrypt")
+        c1, c2 = c1.reshape(n, 64), c2.reshape(n, 64)
+        return (c1, c2) if add is None else (c1, c2, ok)
+
+    def elgamal_rerandomize(self, pk, c1, c2, r, g=None):
+        """C' = C + Enc(0, r): c1 + r * G, c2 + r * PK -> (c1, c2, ok), as elgamal_encrypt(pk, None, r, g, add=(c1, c2)); the m-chain
+        is not run"""
+        return self.elgamal_encrypt(pk, None, r, g=g, add=(c1, c2))
+
+    def elgamal_encrypt_dev(self, pk, d_m, d_r, n, d_c1, d_c2, g=None, d_add_c1=None, d_add_c2=None, d_ok=None, stream=0):
+        """bjj_elgamal_encrypt_dev: d_m = n uint64 or None, d_r = n 32-byte records, d_add_c1 / d_add_c2 = n 64-byte records each
+        or both None, d_c1 / d_c2 = n 64-byte records (they may BE d_add_c1 / d_add_c2: in place), d_ok = n bytes (required with add
+        arrays), on the device"""
+        hg, hpk = self._elgamal_handles(g, pk, "elgamal_encrypt_dev")
+        self._ck(self.lib.bjj_elgamal_encrypt_dev(self.handle, hg, hpk, d_m, d_r, d_add_c1, d_add_c2, n, d_c1, d_c2, d_ok, stream),
+                 "bjj_elgamal_encrypt_dev")
+
     def set_signer_constant_time(self, on=True):
         """signer hardening: public_keys / sign / sign_schnorr scan a small 4-bit table instead of indexing the big one
         with secret digits -- no secret-dependent address or branch; bit-identical results, ~2x slower sign"""
@@ -824,6 +873,10 @@ class FixedBase:
     def mul(self, scalars):
         """scalars[i] * P for every i -> (n, 64): Context.mul_bases with this one base"""
         return self.ctx.mul_bases([self], [scalars])
+
+    def encrypt(self, m, r, g=None, add=None):
+        """exponential ElGamal to THIS point as the public key (Context.elgamal_encrypt)"""
+        return self.ctx.elgamal_encrypt(self, m, r, g=g, add=add)
 
     def verify(self, r_b8, s, msg):
         """EdDSA-Poseidon signatures (R, s) over msg under THIS point as the public key -> (n,) uint8 (Context.eddsa_verify_signer)"""

@@ -43,12 +43,14 @@
 #include "../../include/bjj_hip_dlog.h"
 #include "../../include/bjj_hip_point_sum.h"
 #include "../../include/bjj_hip_common_scalar.h"
+#include "../../include/bjj_hip_elgamal.h"
 #include "bjj_device.hpp"
 #include "bases.hpp"
 #include "signer.hpp"
 #include "signer_set.hpp"
 #include "dlog.hpp"
 #include "common_scalar.hpp"
+#include "elgamal.hpp"
 #include "bjj_launch.hpp"
 #include "msm.hpp"
 #include "copy_pool.hpp"
@@ -261,6 +263,7 @@ struct bjj_ctx {
   int lanes_fixed = 512, lanes_var = 512;
   int lanes_fixed_2x256 = 512;   // resident lanes per CU of K1's two-workgroup shape
   int lanes_bases = 512;         // resident lanes per CU of bjj_k_mul_bases
+  int lanes_elgamal = 512;       // ... of bjj_k_elgamal_encrypt
   int lanes_signer = 512;        // resident lanes per CU of the bjj_k_*_verify_signer kernels
   Handles<bjj_base> user_bases;         // the tables bjj_base_create made and bjj_base_free has not released yet
   int lanes_set = 512;           // resident lanes per CU of the bjj_k_*_verify_set kernels
@@ -692,6 +695,7 @@ int bjj_init(int device, int window_bits, bjj_ctx** out_ctx) {
   c->lanes_fixed = bjjk::fixed_base_lanes_per_cu(0);
   c->lanes_fixed_2x256 = bjjk::fixed_base_lanes_per_cu(1);
   c->lanes_bases = bjjk::bases_lanes_per_cu();
+  c->lanes_elgamal = bjjk::elgamal_lanes_per_cu();
   c->lanes_signer = bjjk::signer_lanes_per_cu();
   c->lanes_set = bjjk::set_lanes_per_cu();
   c->dlog_launch_steps = dlog_launch_steps_from_env();
@@ -2150,6 +2154,7 @@ int bjj_schnorr_verify_set_dev(bjj_ctx* c, const bjj_signer_set* set, const void
 #include "bjj_dlog.inc"
 #include "bjj_point_sum.inc"
 #include "bjj_common_scalar.inc"
+#include "bjj_elgamal.inc"
 
 #pragma GCC visibility pop
 }  // extern "C"

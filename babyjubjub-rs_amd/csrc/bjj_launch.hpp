@@ -20,6 +20,7 @@
 namespace bjj { struct BasesArgs; }   // bases.hpp: the per-base descriptors of bjj_k_mul_bases
 namespace bjj { struct SignerArgs; }  // signer.hpp: the two tables and the point of bjj_k_verify_signer
 namespace bjj { struct SetArgs; }     // signer_set.hpp: the set's tables and keys, the B8 table (bjj_k_verify_set)
+namespace bjj { struct ElgamalArgs; } // elgamal.hpp: the three chains and the input arrays of bjj_k_elgamal_encrypt
 namespace bjj { struct CsDigits; }    // common_scalar.hpp: the recoded scalar of bjj_k_mul_common, by value in the kernel arguments
 
 namespace bjjk {
@@ -187,5 +188,12 @@ enum { COMMON_POINT = 0, COMMON_SUBGROUP = 1, COMMON_DECRYPT = 2 };
 int common_scalar_table_blocks_per_cu();
 hipError_t mul_common(hipStream_t st, int form, int epi, const bjj::CsDigits& D, const uint8_t* pts, const uint8_t* add, size_t n, uint8_t* out,
                       uint8_t* ok, uint32_t* scratch, uint32_t* vb_tables, uint32_t* slotq, uint32_t slot_cap);
+
+// k_elgamal.hip: bjj_elgamal_encrypt -- c1[i] = A1[i] + r[i] G, c2[i] = A2[i] + m[i] G + r[i] PK (elgamal.hpp), one item per lane, one
+// 512-lane workgroup per CU.  A.add_c1 / A.add_c2: both or neither (then ok may be nullptr); out_c1 / out_c2 may be the add arrays
+// themselves; scratch: 2 * n records of 64 bytes
+int elgamal_lanes_per_cu();
+hipError_t elgamal_encrypt(hipStream_t st, int cus, int lanes_per_cu, const bjj::ElgamalArgs& A, size_t n, uint8_t* out_c1, uint8_t* out_c2,
+                           uint8_t* ok, uint32_t* scratch);
 
 }  // namespace bjjk
