@@ -71,39 +71,40 @@ BJJ_HD int base_table_check_slot(const u32* table, const u32* bases, int j, u32 
   return bad;
 }
 
-// sum_j k_j * P_j for ONE item: the chains of fixed_base_mul (base 0: window 0's entry lifted from scratch, no multiplication)
-// and fixed_base_accumulate (every further base: window 0's entry times D', then a 7M addition) run as one stream of
-// additions.  Base 0 starts as fixed_base_mul does, with the gathers of windows 0 and 1 in flight together (hence two staging
-// buffers); from then on one gather is in flight during every addition.  The addition that ends the chain of base j is kept back
-// until the first gather of base j + 1 is issued, so the table reads stay overlapped across the seam, and every addition but the
-// very last of the item produces T (another addition reads it).  `load(j, raw)` hands over the raw 256-bit scalar of base j; the
-// loop over the bases and the mod-l / mod-8l choice depend on the descriptors alone.  G: a gather policy with two staging buffers
-// whose `table` member can be re-pointed.
-template <class G, class LoadScalar>
-BJJ_HD Ext mul_bases_item(const BasesArgs& A, G g, const LoadScalar& load, const Consts& K) {
-  static_assert(G::kBuffers >= 2, "the gathers of windows 0 and 1 of the first base are in flight together");
+// The table-chain walk: sum_j k_j * P_j for ONE item over the t tables of b, where k_j is the scalar `scalar(j, b[j], sc)` delivers
+// ALREADY REDUCED for that table (8 words) and D is any descriptor with `table`, `W` and `nwin` (BaseDesc; EgChain of
+// elgamal.hpp) -- nothing else of a descriptor is read here.  The chains of fixed_base_mul (chain 0: window 0's entry lifted from
+// scratch, no multiplication) and fixed_base_accumulate (every further chain: window 0's entry times D', then a 7M addition) run
+// as one stream of additions.  Chain 0 starts as fixed_base_mul does, with the gathers of windows 0 and 1 in flight together
+// (hence two staging buffers; nwin >= 3 for every table and every W <= 28); from then on one gather is in flight during every
+// addition.  The addition that ends chain j is kept back until the first gather of chain j + 1 is issued, so the table reads
+// stay overlapped across the seam, and every addition but the very last produces T (another addition reads it).  WANT_T: the
+// caller adds to the result, so the last addition produces T too.  G: a gather policy with two staging buffers whose `table`
+// member can be re-pointed.
+template <bool WANT_T, class D, class G, class Scalar>
+BJJ_HD Ext table_chains(const D* b, int t, G g, const Scalar& scalar, const Consts& K) {
+  static_assert(G::kBuffers >= 2, "the gathers of windows 0 and 1 of the first chain are in flight together");
   Ext acc = ext_identity();
   Niels cur = Niels{fr_one(), fr_one(), fr_zero()};
   typename G::Pending p0, p;
   int q = 0;   // staging buffer of the next gather; strictly alternating
   bool neg0, neg;
 #pragma unroll 1
-  for (int j = 0; j < A.t; j++) {
-    const BaseDesc& B = A.b[j];
-    u32 raw[8], sc[8];
-    load(j, raw);
-    if (B.mod_l) scalar_mod_l(raw, sc, K); else scalar_mod_order(raw, sc, K);
+  for (int j = 0; j < t; j++) {
+    const D& B = b[j];
+    u32 sc[8];
+    scalar(j, B, sc);
     DigitStream ds = digit_stream(sc, B.W);
     g.table = B.table;
     g.issue(digit_next(ds, neg0), p0, q);
     if (j == 0) {
-      g.issue(digit_next(ds, neg), p, q ^ 1);                      // window 1 with window 0: nwin >= 9 for every W <= 28
+      g.issue(digit_next(ds, neg), p, q ^ 1);                      // window 1 with window 0
       const Niels n0 = niels_cneg_lazy(g.finish(p0, q), neg0);
       acc.X = fr_reduce_weak(fr_sub(n0.ypx, n0.ymx));              // (2x' : 2y : 2 : 2x'y), as fixed_base_mul
       acc.Y = fr_add(n0.ypx, n0.ymx);
       acc.Z = fr_add(fr_one(), fr_one()); acc.T = fr_add(n0.t2d, fr_zero());
     } else {
-      acc = ext_madd(acc, cur);                                    // the previous base's last addition
+      acc = ext_madd(acc, cur);                                    // the previous chain's last addition
       BJJ_SCHED_FENCE();
       Niels n0 = niels_cneg_lazy(g.finish(p0, q), neg0);
       g.issue(digit_next(ds, neg), p, q ^ 1);
@@ -121,7 +122,19 @@ BJJ_HD Ext mul_bases_item(const BasesArgs& A, G g, const LoadScalar& load, const
       q ^= 1;
     }
   }
-  return ext_madd<false>(acc, cur);   // the item's last addition: the epilogue reads X, Y, Z only
+  return ext_madd<WANT_T>(acc, cur);
+}
+
+// sum_j k_j * P_j for ONE item of bjj_k_mul_bases: the walk over the descriptors of A.  `load(j, raw)` hands over the raw 256-bit
+// scalar of base j; the mod-l / mod-8l choice depends on the descriptor alone.  The item's last addition produces no T: the
+// epilogue reads X, Y, Z only.
+template <class G, class LoadScalar>
+BJJ_HD Ext mul_bases_item(const BasesArgs& A, G g, const LoadScalar& load, const Consts& K) {
+  return table_chains<false>(A.b, A.t, g, [&](int j, const BaseDesc& B, u32 sc[8]) {
+    u32 raw[8];
+    load(j, raw);
+    if (B.mod_l) scalar_mod_l(raw, sc, K); else scalar_mod_order(raw, sc, K);
+  }, K);
 }
 
 }  // namespace bjj

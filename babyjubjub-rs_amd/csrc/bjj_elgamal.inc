@@ -9,10 +9,10 @@ static int elgamal_check(bjj_ctx* c, const bjj_base* g, const bjj_base* pk, cons
   if (!add_c1 != !add_c2) return set_err(BJJ_E_INVALID, std::string(who) + ": the add arrays come both or neither");
   CHECK_N(n);
   memset(A, 0, sizeof(*A));
-  const int gW = g ? g->W : c->W;
-  A->b[0] = EgChain{g ? g->table.p : c->table.p, gW, g ? g->nwin : c->nwin, g ? EG_R_MOD_ORDER : EG_R_MOD_L};
-  A->b[1] = EgChain{A->b[0].table, gW, elgamal_nwin_m(gW), EG_M};
-  A->b[2] = EgChain{pk->table.p, pk->W, pk->nwin, EG_R_MOD_ORDER};
+  const BaseDesc G = base_desc(c, g), P = base_desc(c, pk);
+  A->b[0] = EgChain{G.table, G.W, G.nwin, G.mod_l ? EG_R_MOD_L : EG_R_MOD_ORDER};
+  A->b[1] = EgChain{G.table, G.W, elgamal_nwin_m(G.W), EG_M};
+  A->b[2] = EgChain{P.table, P.W, P.nwin, EG_R_MOD_ORDER};
   return BJJ_OK;
 }
 // One launch on `st`; the set's scratch holds two records per item.
@@ -21,8 +21,6 @@ static hipError_t elgamal_enqueue(bjj_ctx* c, ScratchSet* S, hipStream_t st, Elg
   A.m = (const uint64_t*)m; A.r = (const uint8_t*)r; A.add_c1 = (const uint8_t*)add_c1; A.add_c2 = (const uint8_t*)add_c2;
   return bjjk::elgamal_encrypt(st, c->cus, c->lanes_elgamal, A, n, (uint8_t*)out_c1, (uint8_t*)out_c2, (uint8_t*)ok, S->scratch);
 }
-#define ELGAMAL_DEV_PTR(p, who) \
-  if (!(p) || !aligned16(p)) return set_err(BJJ_E_INVALID, std::string(who) + ": NULL or not 16-byte aligned device pointer")
 #define ELGAMAL_DEV_OPT(p, who) \
   if ((p) && !aligned16(p)) return set_err(BJJ_E_INVALID, std::string(who) + ": not 16-byte aligned device pointer")
 
@@ -32,7 +30,7 @@ int bjj_elgamal_encrypt_dev(bjj_ctx* c, const bjj_base* g, const bjj_base* pk, c
   ElgamalArgs A;
   { int rc = elgamal_check(c, g, pk, d_add_c1_xy, d_add_c2_xy, n, who, &A); if (rc) return rc; }
   if (n == 0) return BJJ_OK;
-  ELGAMAL_DEV_PTR(d_r, who); ELGAMAL_DEV_PTR(d_out_c1_xy, who); ELGAMAL_DEV_PTR(d_out_c2_xy, who);
+  CHECK_PTR(d_r, who); CHECK_PTR(d_out_c1_xy, who); CHECK_PTR(d_out_c2_xy, who);
   ELGAMAL_DEV_OPT(d_m, who); ELGAMAL_DEV_OPT(d_add_c1_xy, who); ELGAMAL_DEV_OPT(d_add_c2_xy, who);
   if (d_add_c1_xy && !d_ok) return set_err(BJJ_E_INVALID, std::string(who) + ": d_ok is NULL (required with add arrays)");
   SET_ENTER(c, stream, 2 * n, false);

@@ -351,10 +351,7 @@ struct bjj_ctx {
 };
 
 static int grid_for(const bjj_ctx* c, size_t n, int blocks_per_cu, int block = BJJ_BLOCK) {
-  size_t want = (n + block - 1) / block;
-  size_t cap = (size_t)c->cus * blocks_per_cu;
-  if (want < 1) want = 1;
-  return (int)(want < cap ? want : cap);
+  return bjjk::capped_grid(n, block, (size_t)c->cus * blocks_per_cu);   // the same number for every n, n = 0 included (one workgroup)
 }
 
 // Which scratch set a call on stream `st` uses:
@@ -955,7 +952,8 @@ int bjj_check_table(bjj_ctx* c, uint64_t* n_bad) {
 // item indices travel as 32-bit words in the work lists and cursors
 #define CHECK_N(n) if ((n) >> 32) return set_err(BJJ_E_INVALID, "batches are limited to 2^32 - 1 items per call")
 #define CHECK_CTX(c, name) if (!(c)) return set_err(BJJ_E_INVALID, name ": ctx is NULL")
-#define CHECK_PTR(p, name) if (!(p) || !aligned16(p)) return set_err(BJJ_E_INVALID, name ": NULL or not 16-byte aligned device pointer")
+#define CHECK_PTR(p, name) \
+  if (!(p) || !aligned16(p)) return set_err(BJJ_E_INVALID, std::string(name) + ": NULL or not 16-byte aligned device pointer")
 // Every *_dev entry selects the context's device (a second context on another GPU of the same process must not launch
 // on a foreign device).  Entries that use scratch (SET_ENTER / SET_LEAVE) pick a scratch set for their stream, size it,
 // order themselves behind the set's previous user and record; the others (DEV_ENTER / DEV_LEAVE) only leave a completion
@@ -1903,6 +1901,11 @@ int bjj_base_check(bjj_ctx* c, const bjj_base* b, uint64_t* n_bad) {
   *n_bad = (uint64_t)bad;
   return BJJ_OK;
 }
+// What the kernels know of the table of `b` (scalar mod 8l), or of the context's B8 table when b is NULL (scalar mod l).  The
+// scalar pointer stays NULL: only bjj_mul_bases has one per base.
+static BaseDesc base_desc(const bjj_ctx* c, const bjj_base* b) {
+  return b ? BaseDesc{b->table.p, nullptr, b->W, b->nwin, 0, 0} : BaseDesc{c->table.p, nullptr, c->W, c->nwin, 1, 0};
+}
 // argument checks of both forms; fills the descriptors but for the scalar pointers
 static int mul_bases_check(bjj_ctx* c, const bjj_base* const* bases, int t, const void* const* scalars, size_t n, const char* who,
                            BasesArgs* A) {
@@ -1916,10 +1919,7 @@ static int mul_bases_check(bjj_ctx* c, const bjj_base* const* bases, int t, cons
     const bjj_base* b = bases[j];
     if (b && !c->user_bases.owns(b)) return set_err(BJJ_E_INVALID, std::string(who) + ": bases[" + std::to_string(j) + "] is not a base of this context");
     if (n && !scalars[j]) return set_err(BJJ_E_INVALID, std::string(who) + ": scalars[" + std::to_string(j) + "] is NULL");
-    A->b[j].table = b ? b->table.p : c->table.p;
-    A->b[j].W = b ? b->W : c->W;
-    A->b[j].nwin = b ? b->nwin : c->nwin;
-    A->b[j].mod_l = b ? 0 : 1;
+    A->b[j] = base_desc(c, b);
   }
   return BJJ_OK;
 }
@@ -1959,8 +1959,8 @@ static int verify_signer_check(bjj_ctx* c, const bjj_base* signer, size_t n, con
   if (!c->user_bases.owns(signer)) return set_err(BJJ_E_INVALID, std::string(who) + ": signer is not a base of this context");
   CHECK_N(n);
   memset(A, 0, sizeof(*A));
-  A->T.table = signer->table.p; A->T.W = signer->W; A->T.nwin = signer->nwin; A->T.mod_l = 0;
-  A->L.table = c->table.p; A->L.W = c->W; A->L.nwin = c->nwin; A->L.mod_l = 1;
+  A->T = base_desc(c, signer);
+  A->L = base_desc(c, nullptr);
   A->pk = signer_point(signer->xy);
   return BJJ_OK;
 }
@@ -2097,8 +2097,8 @@ static int verify_set_check(bjj_ctx* c, const bjj_signer_set* t, size_t n, const
   if (!c->user_sets.owns(t)) return set_err(BJJ_E_INVALID, std::string(who) + ": set is not a signer set of this context");
   CHECK_N(n);
   memset(A, 0, sizeof(*A));
-  A->T.table = t->table.p; A->T.W = t->W; A->T.nwin = t->nwin; A->T.mod_l = 0;
-  A->L.table = c->table.p; A->L.W = c->W; A->L.nwin = c->nwin; A->L.mod_l = 1;
+  A->T = BaseDesc{t->table.p, nullptr, t->W, t->nwin, 0, 0};   // signer 0's table = the base of the allocation
+  A->L = base_desc(c, nullptr);
   A->keys = t->keys.p; A->k = (u32)t->k; A->eps = (u32)set_entries_per_signer(t->W);
   return BJJ_OK;
 }

@@ -31,6 +31,17 @@ static inline int occupancy_of(K kernel, int block) {
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, block, 0) != hipSuccess || nb < 1) nb = 1;
   return nb;
 }
+// resident lanes per CU that serve BOTH of two kernels of one workgroup size: one grid size is computed for the pair
+template <typename Ka, typename Kb>
+static inline int lanes_for_both(Ka a, Kb b, int block) {
+  const int oa = occupancy_of(a, block), ob = occupancy_of(b, block);
+  return (oa < ob ? oa : ob) * block;
+}
+// workgroups of a grid-strided launch over n items: one per `block` items, at least one (n = 0), at most the `cap` resident ones
+static inline int capped_grid(size_t n, int block, size_t cap) {
+  const size_t want = (n + block - 1) / block;
+  return (int)(want < cap ? (want ? want : 1) : cap);
+}
 
 // resident workgroups per CU -- resident LANES per CU for K1 / K2 (queried on the current device)
 int fixed_base_lanes_per_cu(int variant);   // variant 0: one 512-lane workgroup per CU, 1: two 256-lane workgroups

@@ -70,8 +70,7 @@ hipError_t check_base_table(hipStream_t st, int grid, const u32* table, const u3
   return hipGetLastError();
 }
 hipError_t mul_bases(hipStream_t st, int cus, int lanes_per_cu, const BasesArgs& A, size_t n, uint8_t* out, u32* scratch) {
-  const size_t want = (n + BJJ_BASES_BLOCK - 1) / BJJ_BASES_BLOCK, cap = (size_t)cus * (size_t)(lanes_per_cu / BJJ_BASES_BLOCK);
-  const int grid = (int)(want < cap ? (want ? want : 1) : cap);
+  const int grid = capped_grid(n, BJJ_BASES_BLOCK, (size_t)cus * (size_t)(lanes_per_cu / BJJ_BASES_BLOCK));
   BJJ_LAUNCH(bjj_k_mul_bases, dim3(grid), dim3(BJJ_BASES_BLOCK), 0, st, A, n, out, scratch);
   return hipGetLastError();
 }

@@ -64,14 +64,10 @@ __global__ void __launch_bounds__(BJJ_ELGAMAL_BLOCK, 1) bjj_k_elgamal_encrypt_ad
 
 // ---- launchers (declared in bjj_launch.hpp) ------------------------------------------------------------
 namespace bjjk {
-int elgamal_lanes_per_cu() {
-  const int a = occupancy_of(bjj_k_elgamal_encrypt_add, BJJ_ELGAMAL_BLOCK), b = occupancy_of(bjj_k_elgamal_encrypt, BJJ_ELGAMAL_BLOCK);
-  return (a < b ? a : b) * BJJ_ELGAMAL_BLOCK;
-}
+int elgamal_lanes_per_cu() { return lanes_for_both(bjj_k_elgamal_encrypt_add, bjj_k_elgamal_encrypt, BJJ_ELGAMAL_BLOCK); }
 hipError_t elgamal_encrypt(hipStream_t st, int cus, int lanes_per_cu, const ElgamalArgs& A, size_t n, uint8_t* out_c1, uint8_t* out_c2,
                            uint8_t* ok, u32* scratch) {
-  const size_t want = (n + BJJ_ELGAMAL_BLOCK - 1) / BJJ_ELGAMAL_BLOCK, cap = (size_t)cus * (size_t)(lanes_per_cu / BJJ_ELGAMAL_BLOCK);
-  const int grid = (int)(want < cap ? (want ? want : 1) : cap);
+  const int grid = capped_grid(n, BJJ_ELGAMAL_BLOCK, (size_t)cus * (size_t)(lanes_per_cu / BJJ_ELGAMAL_BLOCK));
   if (A.add_c1) BJJ_LAUNCH(bjj_k_elgamal_encrypt_add, dim3(grid), dim3(BJJ_ELGAMAL_BLOCK), 0, st, A, n, out_c1, out_c2, ok, scratch);
   else BJJ_LAUNCH(bjj_k_elgamal_encrypt, dim3(grid), dim3(BJJ_ELGAMAL_BLOCK), 0, st, A, n, out_c1, out_c2, ok, scratch);
   return hipGetLastError();

@@ -493,9 +493,8 @@ __global__ void __launch_bounds__(BJJ_EPI_BLOCK, 1) bjj_k_mul_fixed_base_scan_c3
 // ---- launchers (declared in bjj_launch.hpp) ------------------------------------------------------------
 namespace bjjk {
 int fixed_base_lanes_per_cu(int variant) {   // one grid size serves the affine and the compressed form: the lesser of the two
-  const int a = variant ? occupancy_of(bjj_k_mul_fixed_base_2x256, 256) * 256 : occupancy_of(bjj_k_mul_fixed_base, BJJ_K1_BLOCK) * BJJ_K1_BLOCK;
-  const int b = variant ? occupancy_of(bjj_k_mul_fixed_base_2x256_c32, 256) * 256 : occupancy_of(bjj_k_mul_fixed_base_c32, BJJ_K1_BLOCK) * BJJ_K1_BLOCK;
-  return a < b ? a : b;
+  return variant ? lanes_for_both(bjj_k_mul_fixed_base_2x256, bjj_k_mul_fixed_base_2x256_c32, 256)
+                 : lanes_for_both(bjj_k_mul_fixed_base, bjj_k_mul_fixed_base_c32, BJJ_K1_BLOCK);
 }
 hipError_t fill_fixed_table(hipStream_t st, u32* table, const u32* bases, int W, int nwin) {
   const size_t entries = fixed_stride(W) * (size_t)nwin;
@@ -519,9 +518,8 @@ hipError_t check_fixed_table(hipStream_t st, int grid, const u32* table, const u
 // xy != nullptr: the compressed form (out = 32-byte records, xy = the 64-byte-per-item stash)
 hipError_t mul_fixed_base_scan(hipStream_t st, int cus, const u32* table, int W, int nwin, const uint8_t* scalars, size_t n,
                                uint8_t* out, u32* scratch, uint8_t* xy) {
-  const size_t want = (n + BJJ_EPI_BLOCK - 1) / BJJ_EPI_BLOCK;
-  const size_t cap = (size_t)cus * (size_t)(xy ? occupancy_of(bjj_k_mul_fixed_base_scan_c32, BJJ_EPI_BLOCK) : occupancy_of(bjj_k_mul_fixed_base_scan, BJJ_EPI_BLOCK));
-  const int grid = (int)(want < cap ? (want ? want : 1) : cap);
+  const int occ = xy ? occupancy_of(bjj_k_mul_fixed_base_scan_c32, BJJ_EPI_BLOCK) : occupancy_of(bjj_k_mul_fixed_base_scan, BJJ_EPI_BLOCK);
+  const int grid = capped_grid(n, BJJ_EPI_BLOCK, (size_t)cus * (size_t)occ);
   if (xy)
     BJJ_LAUNCH(bjj_k_mul_fixed_base_scan_c32, dim3(grid), dim3(BJJ_EPI_BLOCK), 0, st, table, W, nwin, scalars, n, out, scratch, xy);
   else
@@ -531,8 +529,7 @@ hipError_t mul_fixed_base_scan(hipStream_t st, int cus, const u32* table, int W,
 hipError_t mul_fixed_base(hipStream_t st, int cus, int lanes_per_cu, int variant, const u32* table, int W, int nwin, const uint8_t* scalars,
                           size_t n, uint8_t* out, u32* scratch, uint8_t* xy) {
   const int block = variant ? 256 : BJJ_K1_BLOCK;
-  const size_t want = (n + block - 1) / block, cap = (size_t)cus * (size_t)(lanes_per_cu / block);
-  const int grid = (int)(want < cap ? (want ? want : 1) : cap);
+  const int grid = capped_grid(n, block, (size_t)cus * (size_t)(lanes_per_cu / block));
   if (xy) {
     if (variant)
       BJJ_LAUNCH(bjj_k_mul_fixed_base_2x256_c32, dim3(grid), dim3(256), 0, st, table, W, nwin, scalars, n, out, scratch, xy);

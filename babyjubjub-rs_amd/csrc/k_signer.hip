@@ -42,14 +42,10 @@ __global__ void __launch_bounds__(BJJ_SIGNER_BLOCK, 2) bjj_k_schnorr_verify_sign
 
 // ---- launchers (declared in bjj_launch.hpp) ------------------------------------------------------------
 namespace bjjk {
-int signer_lanes_per_cu() {   // resident lanes per CU, the lesser of the two kernels: one grid size serves both
-  const int a = occupancy_of(bjj_k_eddsa_verify_signer, BJJ_SIGNER_BLOCK), b = occupancy_of(bjj_k_schnorr_verify_signer, BJJ_SIGNER_BLOCK);
-  return (a < b ? a : b) * BJJ_SIGNER_BLOCK;
-}
+int signer_lanes_per_cu() { return lanes_for_both(bjj_k_eddsa_verify_signer, bjj_k_schnorr_verify_signer, BJJ_SIGNER_BLOCK); }
 hipError_t verify_signer(hipStream_t st, int cus, int lanes_per_cu, bool schnorr, const SignerArgs& A, const uint8_t* r, const uint8_t* s,
                          const uint8_t* msg, size_t n, uint8_t* ok) {
-  const size_t want = (n + BJJ_SIGNER_BLOCK - 1) / BJJ_SIGNER_BLOCK, cap = (size_t)cus * (size_t)(lanes_per_cu / BJJ_SIGNER_BLOCK);
-  const int grid = (int)(want < cap ? (want ? want : 1) : cap);
+  const int grid = capped_grid(n, BJJ_SIGNER_BLOCK, (size_t)cus * (size_t)(lanes_per_cu / BJJ_SIGNER_BLOCK));
   if (schnorr) BJJ_LAUNCH(bjj_k_schnorr_verify_signer, dim3(grid), dim3(BJJ_SIGNER_BLOCK), 0, st, A, r, s, msg, n, ok);
   else BJJ_LAUNCH(bjj_k_eddsa_verify_signer, dim3(grid), dim3(BJJ_SIGNER_BLOCK), 0, st, A, r, s, msg, n, ok);
   return hipGetLastError();

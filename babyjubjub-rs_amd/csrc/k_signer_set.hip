@@ -63,10 +63,7 @@ __global__ void __launch_bounds__(BJJ_SET_BLOCK, 2) bjj_k_schnorr_verify_set(con
 
 // ---- launchers (declared in bjj_launch.hpp) ------------------------------------------------------------
 namespace bjjk {
-int set_lanes_per_cu() {   // resident lanes per CU, the lesser of the two kernels: one grid size serves both
-  const int a = occupancy_of(bjj_k_eddsa_verify_set, BJJ_SET_BLOCK), b = occupancy_of(bjj_k_schnorr_verify_set, BJJ_SET_BLOCK);
-  return (a < b ? a : b) * BJJ_SET_BLOCK;
-}
+int set_lanes_per_cu() { return lanes_for_both(bjj_k_eddsa_verify_set, bjj_k_schnorr_verify_set, BJJ_SET_BLOCK); }
 // the chain length of fill_fixed_table (k_fixed.hip), from the entries of the whole set
 static size_t set_chain(size_t k, int W, int nwin) {
   const size_t chain = (k * fixed_stride(W) * (size_t)nwin) >> 18;
@@ -87,8 +84,7 @@ hipError_t check_signer_set(hipStream_t st, int grid, const u32* table, const u3
 }
 hipError_t verify_set(hipStream_t st, int cus, int lanes_per_cu, bool schnorr, const SetArgs& A, const uint32_t* idx, const uint8_t* r,
                       const uint8_t* s, const uint8_t* msg, size_t n, uint8_t* ok) {
-  const size_t want = (n + BJJ_SET_BLOCK - 1) / BJJ_SET_BLOCK, cap = (size_t)cus * (size_t)(lanes_per_cu / BJJ_SET_BLOCK);
-  const int grid = (int)(want < cap ? (want ? want : 1) : cap);
+  const int grid = capped_grid(n, BJJ_SET_BLOCK, (size_t)cus * (size_t)(lanes_per_cu / BJJ_SET_BLOCK));
   if (schnorr) BJJ_LAUNCH(bjj_k_schnorr_verify_set, dim3(grid), dim3(BJJ_SET_BLOCK), 0, st, A, idx, r, s, msg, n, ok);
   else BJJ_LAUNCH(bjj_k_eddsa_verify_set, dim3(grid), dim3(BJJ_SET_BLOCK), 0, st, A, idx, r, s, msg, n, ok);
   return hipGetLastError();

@@ -333,7 +333,7 @@ hipError_t mul_var_base_main(hipStream_t st, int cus, int lanes_per_cu, int vari
     hipError_t e = hipMemsetAsync(slow, 0, 8 * sizeof(u32), st);
     if (e != hipSuccess) return e;
   }
-  const size_t want = (n + BJJ_K2_BLOCK - 1) / BJJ_K2_BLOCK, cap = (size_t)cus * (size_t)(lanes_per_cu / BJJ_K2_BLOCK);
+  const size_t want = (n + BJJ_K2_BLOCK - 1) / BJJ_K2_BLOCK;   // the tile forms: one workgroup per tile, no cap
   if (xy && variant != 1) return hipErrorInvalidValue;   // the stash apart exists for the tiles only (what the pipeline launches)
   if (variant == 1 && xy) {
   if (sc_words == 8)
@@ -350,7 +350,7 @@ hipError_t mul_var_base_main(hipStream_t st, int cus, int lanes_per_cu, int vari
     BJJ_LAUNCH(bjj_k_mul_var_base_wide_tiles, dim3((unsigned)(want ? want : 1)), dim3(BJJ_K2_BLOCK), 0, st, pts, scalars, sc_words, n, out, scratch,
                        vb_tables, slow, slotq, slot_cap);
   } else {
-  const int grid = (int)(want < cap ? (want ? want : 1) : cap);
+  const int grid = capped_grid(n, BJJ_K2_BLOCK, (size_t)cus * (size_t)(lanes_per_cu / BJJ_K2_BLOCK));
   if (sc_words == 8)
     BJJ_LAUNCH(bjj_k_mul_var_base, dim3(grid), dim3(BJJ_K2_BLOCK), 0, st, pts, scalars, n, out, scratch, vb_tables, slow);
   else

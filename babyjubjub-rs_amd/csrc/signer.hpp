@@ -55,20 +55,23 @@ BJJ_HD int signer_verdict(const Ext& L, const Ext& T, const Fr& rx, const Fr& ry
   return (!fr_is_zero(sum.z) && same_x && same_y) ? 1 : 0;                  // :411 / :384
 }
 
-// One item: verdict 0 / 1 (EdDSA), 0 / 1 / 2 (SCHNORR: 2 = Err, msg > Q) -- what verify_fast_t / verify_exact_t give for
-// pk = the signer's point.  Straight-line: an item whose verdict is known early (msg > Q) runs through the same arithmetic, because
-// the cooperative gather needs every lane of the wave.  Two chains of mul_bases_item, t = 1 each, whose `load` hook hands over a
-// scalar held in registers; T is down to (X, Y, Z) before the second chain starts, and R is read again after it (two
-// multiplications) instead of living through both chains.
-template <bool SCHNORR, class G>
-BJJ_HD int verify_signer_item(const SignerArgs& A, const G& g, const void* r, const void* s, const void* msg, const Consts& K) {
+// One item, from the message read to the verdict: 0 / 1 (EdDSA), 0 / 1 / 2 (SCHNORR: 2 = Err, msg > Q) -- what verify_fast_t /
+// verify_exact_t give for the key pk, whose table dT describes (scalar mod 8l; dL: the context's B8 table, scalar mod l).  The body
+// of bjj_k_verify_signer and of bjj_k_verify_set (signer_set.hpp), which differ in where pk comes from and in how the signer chain
+// gathers: gT is the policy of the chain over dT, gL of the chain over dL.  Straight-line: an item whose verdict is known early
+// (msg > Q) runs through the same arithmetic, because the cooperative gather needs every lane of the wave.  Two chains of
+// mul_bases_item, t = 1 each, whose `load` hook hands over a scalar held in registers; the signer chain's result is down to
+// (X, Y, Z) before the second chain starts, and R is read again after it (two multiplications) instead of living through both.
+template <bool SCHNORR, class GT, class GL>
+BJJ_HD int signer_item_verdict(const BaseDesc& dT, const BaseDesc& dL, const SignerPoint& pk, const GT& gT, const GL& gL, const void* r,
+                               const void* s, const void* msg, const Consts& K) {
   u32 w[8];
   load_w8(msg, w);
   const bool msg_gt = words_gt_modulus(w);                                  // :396-398 / :365-367
   Fr h[5];
   h[4] = fr_to_mont_words(w);                                               // msg == Q wraps to 0, as there
   {
-    const Fr ax = A.pk.x, ay = A.pk.y;
+    const Fr ax = pk.x, ay = pk.y;
     load_w8(r, w);                   const Fr rx = fr_to_mont_words(w);
     load_w8((const char*)r + 32, w); const Fr ry = fr_to_mont_words(w);
     if (SCHNORR) { h[0] = ax; h[1] = ay; h[2] = rx; h[3] = ry; }            // :369
@@ -85,14 +88,14 @@ BJJ_HD int verify_signer_item(const SignerArgs& A, const G& g, const void* r, co
 #pragma unroll
     for (int i = 1; i < 8; i++) kw[i] = (kp[i] << 3) | (kp[i - 1] >> 29);   // 8 (hm mod l) < 8l < 2^254
   }
-  Ext T = mul_bases_item(signer_one_base(A.T), g, [&](int, u32 raw[8]) {
+  Ext T = mul_bases_item(signer_one_base(dT), gT, [&](int, u32 raw[8]) {
 #pragma unroll
     for (int i = 0; i < 8; i++) raw[i] = kw[i];
   }, K);
   T.T = fr_zero();
   u32 sw[8];
   load_w8(s, sw);
-  const Ext L = mul_bases_item(signer_one_base(A.L), g, [&](int, u32 raw[8]) {
+  const Ext L = mul_bases_item(signer_one_base(dL), gL, [&](int, u32 raw[8]) {
 #pragma unroll
     for (int i = 0; i < 8; i++) raw[i] = sw[i];
   }, K);
@@ -101,6 +104,11 @@ BJJ_HD int verify_signer_item(const SignerArgs& A, const G& g, const void* r, co
   load_w8((const char*)r2 + 32, w); const Fr ry = fr_to_mont_words(w);
   const int verdict = signer_verdict(L, T, rx, ry, K);
   return msg_gt ? (SCHNORR ? 2 : 0) : verdict;
+}
+// One item of bjj_k_verify_signer: the key and both gathers are the call's own.
+template <bool SCHNORR, class G>
+BJJ_HD int verify_signer_item(const SignerArgs& A, const G& g, const void* r, const void* s, const void* msg, const Consts& K) {
+  return signer_item_verdict<SCHNORR>(A.T, A.L, A.pk, g, g, r, s, msg, K);
 }
 
 }  // namespace bjj

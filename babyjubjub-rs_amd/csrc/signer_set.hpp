@@ -61,7 +61,7 @@ BJJ_HD void set_window_base(u32* bases, const u32* keys, u64 t, int W, int nwin,
 }
 // Thread t of the fill launch: chain c of window j of signer s, t = (s * nwin + j) * cpw + c.  fixed_table_chain decides T form by
 // "slot0 lies in window 0", so it is handed the signer's OWN table and a slot number inside it: window 0 of every signer comes out
-// in T form, which is what mul_bases_item assumes of a chain's first entry.
+// in T form, which is what table_chains (bases.hpp) assumes of a chain's first entry.
 BJJ_HD void set_fill_chain(u32* table, const u32* bases, u64 t, int W, int nwin, u32 chain, const Consts& K) {
   const u64 stride = fixed_stride(W), cpw = (stride + chain - 1) / chain;
   const u64 sj = t / cpw, k0 = (t % cpw) * chain;
@@ -80,53 +80,18 @@ BJJ_HD int set_check_entry(const u32* table, const u32* bases, const u32* keys, 
 }
 
 // ---- one item ---------------------------------------------------------------------------------------------------------------
-// verify_signer_item (signer.hpp) with the key and the table chosen by the item's index: verdict 0 / 1 (EdDSA), 0 / 1 / 2 (SCHNORR),
+// signer_item_verdict (signer.hpp) with the key and the table chosen by the item's index: verdict 0 / 1 (EdDSA), 0 / 1 / 2 (SCHNORR),
 // or BJJ_SET_BAD_SIGNER for an index >= k.  Such an item runs the arithmetic on signer 0 -- the cooperative gather needs every lane
-// of the wave, and nothing outside the set is read -- and its result is overridden at the end, as for msg > Q.  The signer chain
-// gathers through g with the lane's slot offset idx * eps (< 2^32: set_slots_fit), the B8 chain through g as it is.
+// of the wave, and nothing outside the set is read -- and its result is overridden at the end, before the msg > Q override is
+// looked at.  The signer chain gathers through g with the lane's slot offset idx * eps (< 2^32: set_slots_fit), the B8 chain
+// through g as it is.
 template <bool SCHNORR, class G>
 BJJ_HD int verify_set_item(const SetArgs& A, const G& g, u32 idx, const void* r, const void* s, const void* msg, const Consts& K) {
   const bool bad_idx = idx >= A.k;
   const u32 j = bad_idx ? 0u : idx;
-  u32 w[8];
-  load_w8(msg, w);
-  const bool msg_gt = words_gt_modulus(w);                                  // :396-398 / :365-367
-  Fr h[5];
-  h[4] = fr_to_mont_words(w);                                               // msg == Q wraps to 0, as there
-  {
-    const SignerPoint pk = set_key_load(A.keys + (size_t)j * SET_KEY_WORDS);
-    load_w8(r, w);                   const Fr rx = fr_to_mont_words(w);
-    load_w8((const char*)r + 32, w); const Fr ry = fr_to_mont_words(w);
-    if (SCHNORR) { h[0] = pk.x; h[1] = pk.y; h[2] = rx; h[3] = ry; }        // :369
-    else         { h[0] = rx; h[1] = ry; h[2] = pk.x; h[3] = pk.y; }        // :400
-  }
-  const Fr hm_plain = fr_canon(fr_mul(poseidon5_t<true>(h, K), fr_one_plain()));
-  u32 kw[8];
-  if (SCHNORR) {
-    fr_to_words(hm_plain, kw);                                              // hm < r; the chain reduces it mod 8l
-  } else {
-    u32 kp[8];
-    fr_to_words(plain_mod_l(hm_plain, K), kp);
-    kw[0] = kp[0] << 3;
-#pragma unroll
-    for (int i = 1; i < 8; i++) kw[i] = (kp[i] << 3) | (kp[i - 1] >> 29);   // 8 (hm mod l) < 8l < 2^254
-  }
-  Ext T = mul_bases_item(signer_one_base(A.T), gather_slot_offset(g, (size_t)j * A.eps), [&](int, u32 raw[8]) {
-#pragma unroll
-    for (int i = 0; i < 8; i++) raw[i] = kw[i];
-  }, K);
-  T.T = fr_zero();
-  u32 sw[8];
-  load_w8(s, sw);
-  const Ext L = mul_bases_item(signer_one_base(A.L), g, [&](int, u32 raw[8]) {
-#pragma unroll
-    for (int i = 0; i < 8; i++) raw[i] = sw[i];
-  }, K);
-  const void* r2 = signer_reload(r);
-  load_w8(r2, w);                   const Fr rx = fr_to_mont_words(w);
-  load_w8((const char*)r2 + 32, w); const Fr ry = fr_to_mont_words(w);
-  const int verdict = signer_verdict(L, T, rx, ry, K);
-  return bad_idx ? BJJ_SET_BAD_SIGNER : msg_gt ? (SCHNORR ? 2 : 0) : verdict;
+  const int verdict = signer_item_verdict<SCHNORR>(A.T, A.L, set_key_load(A.keys + (size_t)j * SET_KEY_WORDS),
+                                                   gather_slot_offset(g, (size_t)j * A.eps), g, r, s, msg, K);
+  return bad_idx ? BJJ_SET_BAD_SIGNER : verdict;
 }
 
 }  // namespace bjj

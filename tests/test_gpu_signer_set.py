@@ -142,7 +142,7 @@ def test_byte_offsets_beyond_4_gib(oracle, keys, set768, schnorr):
 
 # ---- 3 ---------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("schnorr", [False, True], ids=["eddsa", "schnorr"])
-def test_out_of_range_indices_are_data(gpu_ctx, sets, data, schnorr):
+def test_out_of_range_indices_are_data(gpu_ctx, oracle, keys, sets, data, schnorr):
     k, W, n = 65, 4, 513
     sset = sets("gpu_ctx", k, W)
     p = _take(data(k, schnorr), np.arange(NMAX - n, NMAX))
@@ -152,9 +152,13 @@ def test_out_of_range_indices_are_data(gpu_ctx, sets, data, schnorr):
         idx[i] = v
     want = p["want"].copy()
     want[list(where)] = BAD
+    msg = p["msg"].copy()
+    msg[63] = ssc.sc.rec([ssc.Q + 7])[0]                    # msg > Q (Schnorr: 2, EdDSA: 0) under an index outside the set: still 3
+    under_0 = (oracle.verify_schnorr if schnorr else oracle.verify)(keys(k)[3][:1], p["R"][63:64], p["S"][63:64], msg[63:64])
+    assert under_0.tolist() == [2 if schnorr else 0]       # what signer 0, whose tables such an item walks, alone would give
     ok = np.full(n, 0xEE, np.uint8)
     fn = gpu_ctx.lib.bjj_schnorr_verify_set if schnorr else gpu_ctx.lib.bjj_eddsa_verify_set
-    rc = fn(gpu_ctx.handle, sset.handle, idx.ctypes.data, p["R"].ctypes.data, p["S"].ctypes.data, p["msg"].ctypes.data, n, ok.ctypes.data)
+    rc = fn(gpu_ctx.handle, sset.handle, idx.ctypes.data, p["R"].ctypes.data, p["S"].ctypes.data, msg.ctypes.data, n, ok.ctypes.data)
     assert rc == 0, gpu_ctx.lib.bjj_last_error()
     bad = np.nonzero(ok != want)[0]
     assert bad.size == 0, bad[:8].tolist()

@@ -33,7 +33,7 @@ def _build(exe, san):
 def inputs(oracle, pyoracle, golden):
     """the program's stdin and the expected verdicts -- computed once.  Keys: ordinary, of order 8l, ordinary with x + r in its
     record.  Items: the directed ones under keys 0 (both schemes) and 1 (EdDSA), a few signed ones under every key, four of them
-    presented under another signer's index, and three whose index is not one of the set."""
+    presented under another signer's index, and three whose index is not one of the set, one of these with msg > Q as well."""
     o = pyoracle
     tors = [ints(t) for t in golden["gpu_expected"]["torsion_points"]]
     scalars = [sc.KEY_SCALAR, sc.KEY_SCALAR + 12345, sc.KEY_SCALAR + 999]
@@ -64,6 +64,9 @@ def inputs(oracle, pyoracle, golden):
     idx = [idx[i] for i in perm]
     Rv, Sv, Mv = ([unpack(a, w)[i] for i in perm] for a, w in ((R, 2), (S, 1), (M, 1)))
     assert {0, K - 1} <= set(idx) and sum(i >= K for i in idx) == 3
+    both = idx.index(K + 1)                                # one of them also carries msg > Q: the index is looked at first
+    Mv[both] = Q + 7
+    assert o.verify_schnorr(keys[0], Mv[both], Rv[both], Sv[both]) is None and not o.verify(keys[0], Rv[both], Sv[both], Mv[both])
     text = "K %d\n%s\nI %d\n%s\n" % (K, "\n".join("%x %x" % p for p in records), n,
                                      "\n".join("%x %x %x %x %x" % (idx[i], Rv[i][0], Rv[i][1], Sv[i], Mv[i]) for i in range(n)))
     ed, sn = [], []
@@ -79,6 +82,7 @@ def inputs(oracle, pyoracle, golden):
     for j in range(K):
         assert {ed[i] for i in range(n) if idx[i] == j} == {0, 1}, j
     assert set(ed) == {0, 1, 3} and set(sn) == {0, 1, 2, 3}
+    assert ed[both] == BAD_SIGNER and sn[both] == BAD_SIGNER
     return {"text": text, "n": n, "eddsa": ed, "schnorr": sn}
 
 
