@@ -45,6 +45,13 @@ struct Consts {
   Fr TSH[448];
   unsigned char TSHASH[2048];
 };
+// The one initialiser of Consts: the BJJ_K_* lists of bjj_constants.inc (include it where this is used) in MEMBER ORDER.  Edit the
+// struct and this list together: a member added or moved in one of them only initialises the wrong member without a warning.
+#define BJJ_CONSTS_INIT                                                                                                            \
+  { BJJ_K_A, BJJ_K_D, BJJ_K_F, BJJ_K_FINV_PLAIN, BJJ_K_FINV, BJJ_K_L_R1, BJJ_K_L_R2, BJJ_K_DP, BJJ_K_D2P, BJJ_K_DPINV, BJJ_K_B8X,   \
+    BJJ_K_B8Y, BJJ_K_TS_G, BJJ_K_HALFQ, BJJ_K_ORDER, BJJ_K_ORDER2, BJJ_K_ORDER4, BJJ_K_L, BJJ_K_L2, BJJ_K_L4, BJJ_K_POSEIDON_CF,   \
+    BJJ_K_POSEIDON_KP, BJJ_K_POSEIDON_SP, BJJ_K_POSEIDON_AL, BJJ_K_POSEIDON_M, BJJ_K_POSEIDON_CAB, BJJ_K_TS_NEG, BJJ_K_TS_HALF,    \
+    BJJ_K_TS_HASH }
 
 struct Ext { Fr X, Y, Z, T; };            // a' = -1 curve, extended
 struct Niels { Fr ymx, ypx, t2d; };       // affine point (x',y): y-x', y+x', 2D'x'y

@@ -8,19 +8,8 @@
 #include <vector>
 #include "../../babyjubjub-rs_amd/csrc/common_scalar.hpp"
 #include "../../babyjubjub-rs_amd/csrc/bjj_constants.inc"
-using namespace bjj;
-static const Consts K = {
-    BJJ_K_A, BJJ_K_D, BJJ_K_F, BJJ_K_FINV_PLAIN, BJJ_K_FINV, BJJ_K_L_R1, BJJ_K_L_R2, BJJ_K_DP, BJJ_K_D2P, BJJ_K_DPINV, BJJ_K_B8X, BJJ_K_B8Y, BJJ_K_TS_G, BJJ_K_HALFQ,
-    BJJ_K_ORDER, BJJ_K_ORDER2, BJJ_K_ORDER4, BJJ_K_L, BJJ_K_L2, BJJ_K_L4,
-    BJJ_K_POSEIDON_CF, BJJ_K_POSEIDON_KP, BJJ_K_POSEIDON_SP, BJJ_K_POSEIDON_AL, BJJ_K_POSEIDON_M, BJJ_K_POSEIDON_CAB,
-    BJJ_K_TS_NEG, BJJ_K_TS_HALF, BJJ_K_TS_HASH};
+#include "../emul_support.hpp"
 
-template <typename T>
-struct Aligned {   // 16-byte aligned storage (load_w8 / store_w8 move 16-byte quarters)
-  std::vector<T> v;
-  explicit Aligned(size_t n) : v(n + 16 / sizeof(T) + 1) {}
-  T* p() { return (T*)(((uintptr_t)v.data() + 15) & ~(uintptr_t)15); }
-};
 constexpr u32 GUARD = 0xdeadbeefu;
 constexpr int GUARD_WORDS = 8;
 
@@ -33,12 +22,9 @@ static void plan(const uint8_t scalar[32], bool negate, int form, CsDigits* D) {
 template <bool TABLE, bool ADD>
 static int item_point(const uint8_t* pts, const uint8_t* add, size_t i, const CsDigits& D, u32* tbl, uint8_t* out) {
   Ext p;
-  u32 w[8];
   if (!cs_item<TABLE, ADD>(pts, add, i, D, tbl, p, K)) { memset(out, 0, 64); return 2; }
   if (fr_is_zero(p.Z)) return -3;   // the Z of a sum of curve points is never 0
-  const Fr zi = fr_inv(p.Z);
-  fr_from_mont_words(fr_mul(fr_mul(p.X, zi), K.FINV), w); memcpy(out, w, 32);
-  fr_from_mont_words(fr_mul(p.Y, zi), w);                 memcpy(out + 32, w, 32);
+  store_affine(out, p);
   return 1;
 }
 template <bool TABLE>

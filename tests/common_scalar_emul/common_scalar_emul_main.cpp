@@ -5,13 +5,6 @@
 #include <stdio.h>
 #include "common_scalar_emul.cpp"
 
-static void store_affine(uint8_t* out, const Ext& p) {
-  u32 w[8];
-  const Fr zi = fr_inv(p.Z);
-  fr_from_mont_words(fr_mul(fr_mul(p.X, zi), K.FINV), w); memcpy(out, w, 32);
-  fr_from_mont_words(fr_mul(p.Y, zi), w);                 memcpy(out + 32, w, 32);
-}
-
 int main() {
   const size_t n = 40, bad = 17, zero = 29;
   std::vector<uint8_t> pts(n * 64), add(n * 64);

@@ -27,37 +27,9 @@
 #include <vector>
 #include "../../babyjubjub-rs_amd/csrc/dlog.hpp"
 #include "../../babyjubjub-rs_amd/csrc/bjj_constants.inc"
-using namespace bjj;
-static const Consts K = {
-    BJJ_K_A, BJJ_K_D, BJJ_K_F, BJJ_K_FINV_PLAIN, BJJ_K_FINV, BJJ_K_L_R1, BJJ_K_L_R2, BJJ_K_DP, BJJ_K_D2P, BJJ_K_DPINV, BJJ_K_B8X, BJJ_K_B8Y, BJJ_K_TS_G, BJJ_K_HALFQ,
-    BJJ_K_ORDER, BJJ_K_ORDER2, BJJ_K_ORDER4, BJJ_K_L, BJJ_K_L2, BJJ_K_L4,
-    BJJ_K_POSEIDON_CF, BJJ_K_POSEIDON_KP, BJJ_K_POSEIDON_SP, BJJ_K_POSEIDON_AL, BJJ_K_POSEIDON_M, BJJ_K_POSEIDON_CAB,
-    BJJ_K_TS_NEG, BJJ_K_TS_HALF, BJJ_K_TS_HASH};
+#include "../emul_support.hpp"
 
-struct Words { alignas(16) u32 w[8]; };
-static bool parse_hex(const char* s, Words& out) {
-  const size_t len = strlen(s);
-  if (len == 0 || len > 64) return false;
-  memset(out.w, 0, sizeof(out.w));
-  for (size_t i = 0; i < len; i++) {
-    const char c = s[len - 1 - i];
-    const int v = c >= '0' && c <= '9' ? c - '0' : c >= 'a' && c <= 'f' ? c - 'a' + 10 : -1;
-    if (v < 0) return false;
-    out.w[i / 8] |= (u32)v << (4 * (i % 8));
-  }
-  return true;
-}
-static bool read_words(Words* out, size_t count) {
-  char tok[80];
-  for (size_t i = 0; i < count; i++)
-    if (scanf("%79s", tok) != 1 || !parse_hex(tok, out[i])) return false;
-  return true;
-}
-static bool read_tag(const char* name) {
-  char tok[80];
-  return scanf("%79s", tok) == 1 && !strcmp(tok, name);
-}
-static void print_hex(const u32 w[8]) {
+static void print_hex_short(const u32 w[8]) {   // without leading zeros
   int top = 7;
   while (top > 0 && w[top] == 0) top--;
   printf("%x", w[top]);
@@ -179,11 +151,11 @@ int main() {
   size_t nr = 0, ni = 0;
   if (!read_tag("G") || !read_words(gxy, 2)) { fprintf(stderr, "bad G line\n"); return 2; }
   if (!read_tag("T") || scanf("%d %u", &g_b, &chain) != 2 || g_b < BJJ_DLOG_MIN_BABY_BITS || g_b > 12 || chain < 1) { fprintf(stderr, "bad T line\n"); return 2; }
-  if (!read_tag("R") || scanf("%zu", &nr) != 1 || nr > 16) { fprintf(stderr, "bad R line\n"); return 2; }
+  if (!read_header("R", nr) || nr > 16) { fprintf(stderr, "bad R line\n"); return 2; }
   std::vector<int> ranges(nr);
   for (size_t i = 0; i < nr; i++)
     if (scanf("%d", &ranges[i]) != 1 || ranges[i] < 1 || ranges[i] > dlog_max_range_bits(g_b)) { fprintf(stderr, "bad range\n"); return 2; }
-  if (!read_tag("I") || scanf("%zu", &ni) != 1 || ni > 100000) { fprintf(stderr, "bad I line\n"); return 2; }
+  if (!read_header("I", ni)) { fprintf(stderr, "bad I line\n"); return 2; }
   std::vector<Words> items(2 * ni + 1);
   if (!read_words(items.data(), 2 * ni)) { fprintf(stderr, "bad item\n"); return 2; }
   items.resize(2 * ni);
@@ -192,7 +164,7 @@ int main() {
   if (!ref_on_curve(bx, by, K)) { fprintf(stderr, "the base is not on the curve\n"); return 2; }
   dlog_setup(g_params, bx, by, g_b, K);
   printf("small %u\n", g_params[DLOG_P_SMALL]);
-  printf("base "); print_hex(g_params + DLOG_P_XY); printf(" "); print_hex(g_params + DLOG_P_XY + 8); printf("\n");
+  printf("base "); print_hex_short(g_params + DLOG_P_XY); printf(" "); print_hex_short(g_params + DLOG_P_XY + 8); printf("\n");
   if (g_params[DLOG_P_SMALL]) return 0;
   run<32>(chain, ranges, items);
   run<3>(chain, ranges, items);

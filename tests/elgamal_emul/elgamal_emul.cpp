@@ -9,34 +9,9 @@
 #include <vector>
 #include "../../babyjubjub-rs_amd/csrc/elgamal.hpp"
 #include "../../babyjubjub-rs_amd/csrc/bjj_constants.inc"
-using namespace bjj;
-static const Consts K = {
-    BJJ_K_A, BJJ_K_D, BJJ_K_F, BJJ_K_FINV_PLAIN, BJJ_K_FINV, BJJ_K_L_R1, BJJ_K_L_R2, BJJ_K_DP, BJJ_K_D2P, BJJ_K_DPINV, BJJ_K_B8X, BJJ_K_B8Y, BJJ_K_TS_G, BJJ_K_HALFQ,
-    BJJ_K_ORDER, BJJ_K_ORDER2, BJJ_K_ORDER4, BJJ_K_L, BJJ_K_L2, BJJ_K_L4,
-    BJJ_K_POSEIDON_CF, BJJ_K_POSEIDON_KP, BJJ_K_POSEIDON_SP, BJJ_K_POSEIDON_AL, BJJ_K_POSEIDON_M, BJJ_K_POSEIDON_CAB,
-    BJJ_K_TS_NEG, BJJ_K_TS_HALF, BJJ_K_TS_HASH};
+#include "../emul_support.hpp"
 
-template <typename T>
-struct Aligned {   // 16-byte aligned storage (load_w8 / store_w8 move 16-byte quarters)
-  std::vector<T> v;
-  explicit Aligned(size_t n) : v(n + 16 / sizeof(T) + 1) {}
-  T* p() { return (T*)(((uintptr_t)v.data() + 15) & ~(uintptr_t)15); }
-};
-
-struct Table {
-  int W, nwin;
-  bool ctx_b8;   // the context's B8 table: fixed_nwin windows, r mod l
-  Aligned<u32> words;
-  Table(int W_, int nwin_, bool ctx) : W(W_), nwin(nwin_), ctx_b8(ctx), words(fixed_stride(W_) * (size_t)nwin_ * NIELS_WORDS) {}
-};
-static std::vector<std::unique_ptr<Table>> g_tables;
-
-static void store_affine(uint8_t* out, const Ext& p) {
-  u32 w[8];
-  const Fr zi = fr_inv(p.Z);
-  fr_from_mont_words(fr_mul(fr_mul(p.X, zi), K.FINV), w); memcpy(out, w, 32);
-  fr_from_mont_words(fr_mul(p.Y, zi), w);                 memcpy(out + 32, w, 32);
-}
+static std::vector<std::unique_ptr<HostTable>> g_tables;
 
 extern "C" {
 int eg_emul_nwin_m(int W) { return elgamal_nwin_m(W); }
@@ -50,22 +25,9 @@ int eg_emul_table(const uint8_t* xy, int W) {
     bx = fr_to_mont_words(w); by = fr_to_mont_words(w + 8);
     if (!ref_on_curve(bx, by, K)) return -1;
   }
-  const int nwin = xy ? base_nwin(W) : fixed_nwin(W);
-  std::unique_ptr<Table> t(new Table(W, nwin, !xy));
-  u32* tab = t->words.p();
-  const size_t stride = fixed_stride(W);
-  for (int j = 0; j < nwin; j++) {
-    const Niels base = base_table_entry(bx, by, 1u, j, W, K);
-    for (size_t k0 = 0; k0 < stride; k0 += 1024) {
-      const u32 cnt = (u32)(stride - k0 < 1024 ? stride - k0 : 1024);
-      fixed_table_chain(tab, base, (size_t)j * stride + k0, (u32)k0, cnt, W, K);
-    }
-  }
-  const size_t slots = stride * (size_t)nwin, step = slots > 400 ? slots / 97 : 1;
-  for (size_t s = 0; s < slots; s += step) {
-    const int j = (int)(s / stride);
-    if (!niels_limbs_equal(load_niels(tab + s * NIELS_WORDS), base_table_entry(bx, by, (u32)(s % stride), j, W, K, j == 0))) return -2;
-  }
+  std::unique_ptr<HostTable> t(new HostTable);
+  t->build(bx, by, W, !xy, 1024);
+  if (t->entry_mismatches(t->slots() > 400 ? t->slots() / 97 : 1)) return -2;
   g_tables.push_back(std::move(t));
   return (int)g_tables.size() - 1;
 }
@@ -87,8 +49,8 @@ int eg_emul_encrypt(int g, int pk, const uint64_t* m, const uint8_t* r, const ui
                     uint8_t* out_c1, uint8_t* out_c2, uint8_t* ok) {
   if (g < 0 || pk < 0 || (size_t)g >= g_tables.size() || (size_t)pk >= g_tables.size() || !add_c1 != !add_c2 || g_tables[pk]->ctx_b8) return -1;
   if (in_place && !add_c1) return -1;
-  Table& tg = *g_tables[g];
-  Table& tp = *g_tables[pk];
+  HostTable& tg = *g_tables[g];
+  HostTable& tp = *g_tables[pk];
   Aligned<uint8_t> in_r(n * 32 + 1), a1(n * 64 + 1), a2(n * 64 + 1), o1(n * 64 + 1), o2(n * 64 + 1);
   Aligned<uint64_t> in_m(n + 1);
   if (n) memcpy(in_r.p(), r, n * 32);
@@ -98,9 +60,9 @@ int eg_emul_encrypt(int g, int pk, const uint64_t* m, const uint8_t* r, const ui
   if (n && add_c1) { memcpy(s1, add_c1, n * 64); memcpy(s2, add_c2, n * 64); }
   ElgamalArgs A;
   memset(&A, 0, sizeof(A));
-  A.b[0] = EgChain{tg.words.p(), tg.W, tg.nwin, tg.ctx_b8 ? EG_R_MOD_L : EG_R_MOD_ORDER};
+  A.b[0] = EgChain{tg.t(), tg.W, tg.nwin, tg.ctx_b8 ? EG_R_MOD_L : EG_R_MOD_ORDER};
   A.b[1] = EgChain{A.b[0].table, tg.W, elgamal_nwin_m(tg.W), EG_M};
-  A.b[2] = EgChain{tp.words.p(), tp.W, tp.nwin, EG_R_MOD_ORDER};
+  A.b[2] = EgChain{tp.t(), tp.W, tp.nwin, EG_R_MOD_ORDER};
   A.m = m ? in_m.p() : nullptr; A.r = in_r.p();
   A.add_c1 = add_c1 ? s1 : nullptr; A.add_c2 = add_c1 ? s2 : nullptr;
   int bad = 0;

@@ -10,11 +10,7 @@
 #include "../../babyjubjub-rs_amd/csrc/bjj_constants.inc"
 #include "../devfuzz/curve_ops.hpp"
 using namespace bjj;
-static const Consts K = {
-    BJJ_K_A, BJJ_K_D, BJJ_K_F, BJJ_K_FINV_PLAIN, BJJ_K_FINV, BJJ_K_L_R1, BJJ_K_L_R2, BJJ_K_DP, BJJ_K_D2P, BJJ_K_DPINV, BJJ_K_B8X, BJJ_K_B8Y, BJJ_K_TS_G, BJJ_K_HALFQ,
-    BJJ_K_ORDER, BJJ_K_ORDER2, BJJ_K_ORDER4, BJJ_K_L, BJJ_K_L2, BJJ_K_L4,
-    BJJ_K_POSEIDON_CF, BJJ_K_POSEIDON_KP, BJJ_K_POSEIDON_SP, BJJ_K_POSEIDON_AL, BJJ_K_POSEIDON_M, BJJ_K_POSEIDON_CAB,
-    BJJ_K_TS_NEG, BJJ_K_TS_HALF, BJJ_K_TS_HASH};
+static const Consts K = BJJ_CONSTS_INIT;
 
 // a: n records of curve_words(op, 0) words, b: n of curve_words(op, 1) (may be null when 0), out: n of curve_words(op, 2);
 // the per-item scratch (curve_words(op, 3) words) is one 16-byte aligned block here, reused item after item

@@ -15,14 +15,7 @@
 #include <vector>
 #include "../../babyjubjub-rs_amd/csrc/sign.hpp"
 #include "../../babyjubjub-rs_amd/csrc/bjj_constants.inc"
-using namespace bjj;
-static const Consts K = {
-    BJJ_K_A, BJJ_K_D, BJJ_K_F, BJJ_K_FINV_PLAIN, BJJ_K_FINV, BJJ_K_L_R1, BJJ_K_L_R2, BJJ_K_DP, BJJ_K_D2P, BJJ_K_DPINV, BJJ_K_B8X, BJJ_K_B8Y, BJJ_K_TS_G, BJJ_K_HALFQ,
-    BJJ_K_ORDER, BJJ_K_ORDER2, BJJ_K_ORDER4, BJJ_K_L, BJJ_K_L2, BJJ_K_L4,
-    BJJ_K_POSEIDON_CF, BJJ_K_POSEIDON_KP, BJJ_K_POSEIDON_SP, BJJ_K_POSEIDON_AL, BJJ_K_POSEIDON_M, BJJ_K_POSEIDON_CAB,
-    BJJ_K_TS_NEG, BJJ_K_TS_HALF, BJJ_K_TS_HASH};
-
-static int hexval(int c) { return c >= '0' && c <= '9' ? c - '0' : c >= 'a' && c <= 'f' ? c - 'a' + 10 : c >= 'A' && c <= 'F' ? c - 'A' + 10 : -1; }
+#include "../emul_support.hpp"
 
 // gather policy (bjj_device.hpp "gather policies") over a table that exists one entry at a time
 struct Entries {
@@ -92,24 +85,19 @@ static void affine_words(const Ext& p, u32 x[8], u32 y[8]) {   // canonical x', 
 int main() {
   char line[256];
   while (fgets(line, sizeof line, stdin)) {
-    char* p = line;
-    const int W = (int)strtol(p, &p, 10);
-    while (*p == ' ') p++;
-    alignas(16) u32 raw[8] = {0};
-    int n = 0;
-    for (; n < 64 && hexval(p[n]) >= 0; n++) {}
-    if (n != 64 || W < 4 || W > 28) { fprintf(stderr, "bad input line: %s", line); return 2; }
-    for (int i = 0; i < 64; i++) raw[7 - i / 8] |= (u32)hexval(p[i]) << (4 * (7 - i % 8));
+    int W = 0;
+    char tok[80];
+    Words raw;
+    if (sscanf(line, "%d %79s", &W, tok) != 2 || strlen(tok) != 64 || !parse_hex(tok, raw) || W < 4 || W > 28) { fprintf(stderr, "bad input line: %s", line); return 2; }
     g_entries.width(W);
     const int nwin = fixed_nwin(W);
-    const Ext got = sign_carry_mul(W, nwin, raw);
-    const Ext want = fixed_base_mul(GatherHost(), W, nwin, raw, K);
+    const Ext got = sign_carry_mul(W, nwin, raw.w);
+    const Ext want = fixed_base_mul(GatherHost(), W, nwin, raw.w, K);
     u32 gx[8], gy[8], wx[8], wy[8];
     affine_words(got, gx, gy);
     affine_words(want, wx, wy);
     const int bad = (memcmp(gx, wx, 32) != 0) + (memcmp(gy, wy, 32) != 0) + g_entries.bad;
-    printf("%d %d %08x%08x%08x%08x%08x%08x%08x%08x %08x%08x%08x%08x%08x%08x%08x%08x\n", W, bad,
-           gx[7], gx[6], gx[5], gx[4], gx[3], gx[2], gx[1], gx[0], gy[7], gy[6], gy[5], gy[4], gy[3], gy[2], gy[1], gy[0]);
+    printf("%d %d ", W, bad); print_hex(gx); printf(" "); print_hex(gy); printf("\n");
   }
   return 0;
 }

@@ -10,14 +10,7 @@
 #include <stdlib.h>
 #include "../../babyjubjub-rs_amd/csrc/sign.hpp"
 #include "../../babyjubjub-rs_amd/csrc/bjj_constants.inc"
-using namespace bjj;
-static const Consts K = {
-    BJJ_K_A, BJJ_K_D, BJJ_K_F, BJJ_K_FINV_PLAIN, BJJ_K_FINV, BJJ_K_L_R1, BJJ_K_L_R2, BJJ_K_DP, BJJ_K_D2P, BJJ_K_DPINV, BJJ_K_B8X, BJJ_K_B8Y, BJJ_K_TS_G, BJJ_K_HALFQ,
-    BJJ_K_ORDER, BJJ_K_ORDER2, BJJ_K_ORDER4, BJJ_K_L, BJJ_K_L2, BJJ_K_L4,
-    BJJ_K_POSEIDON_CF, BJJ_K_POSEIDON_KP, BJJ_K_POSEIDON_SP, BJJ_K_POSEIDON_AL, BJJ_K_POSEIDON_M, BJJ_K_POSEIDON_CAB,
-    BJJ_K_TS_NEG, BJJ_K_TS_HALF, BJJ_K_TS_HASH};
-
-static int hexval(int c) { return c >= '0' && c <= '9' ? c - '0' : c >= 'a' && c <= 'f' ? c - 'a' + 10 : c >= 'A' && c <= 'F' ? c - 'A' + 10 : -1; }
+#include "../emul_support.hpp"
 
 // one width: returns the number of failed checks; prints the digits when asked
 static int check_width(const u32 sc[8], int W, bool print) {
@@ -58,15 +51,14 @@ int main() {
     const char* p = line;
     bool print = false;
     if (p[0] == 'D' && p[1] == ' ') { print = true; p += 2; }
-    alignas(16) u32 raw[8] = {0}, sc[8];
-    int n = 0;
-    for (; n < 64 && hexval(p[n]) >= 0; n++) {}
-    if (n != 64) { fprintf(stderr, "bad input line: %s", line); return 2; }
-    for (int i = 0; i < 64; i++) raw[7 - i / 8] |= (u32)hexval(p[i]) << (4 * (7 - i % 8));
-    scalar_mod_l_weak(raw, sc, K);
+    Words raw;
+    alignas(16) u32 sc[8];
+    char tok[80];
+    if (sscanf(p, "%79s", tok) != 1 || strlen(tok) != 64 || !parse_hex(tok, raw)) { fprintf(stderr, "bad input line: %s", line); return 2; }
+    scalar_mod_l_weak(raw.w, sc, K);
     int bad = 0;
     for (int W = 4; W <= 28; W++) bad += check_width(sc, W, false);
-    printf("%08x%08x%08x%08x%08x%08x%08x%08x %d\n", sc[7], sc[6], sc[5], sc[4], sc[3], sc[2], sc[1], sc[0], bad);
+    print_hex(sc); printf(" %d\n", bad);
     if (print)
       for (int W = 4; W <= 28; W++) check_width(sc, W, true);
   }

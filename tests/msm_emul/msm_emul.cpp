@@ -6,19 +6,7 @@
 #include <vector>
 #include "../../babyjubjub-rs_amd/csrc/msm.hpp"
 #include "../../babyjubjub-rs_amd/csrc/bjj_constants.inc"
-using namespace bjj;
-static const Consts K = {
-    BJJ_K_A, BJJ_K_D, BJJ_K_F, BJJ_K_FINV_PLAIN, BJJ_K_FINV, BJJ_K_L_R1, BJJ_K_L_R2, BJJ_K_DP, BJJ_K_D2P, BJJ_K_DPINV, BJJ_K_B8X, BJJ_K_B8Y, BJJ_K_TS_G, BJJ_K_HALFQ,
-    BJJ_K_ORDER, BJJ_K_ORDER2, BJJ_K_ORDER4, BJJ_K_L, BJJ_K_L2, BJJ_K_L4,
-    BJJ_K_POSEIDON_CF, BJJ_K_POSEIDON_KP, BJJ_K_POSEIDON_SP, BJJ_K_POSEIDON_AL, BJJ_K_POSEIDON_M, BJJ_K_POSEIDON_CAB,
-    BJJ_K_TS_NEG, BJJ_K_TS_HALF, BJJ_K_TS_HASH};
-
-template <typename T>
-struct Aligned {   // 16-byte aligned storage (load_w8 / load_niels read 16-byte quarters)
-  std::vector<T> v;
-  explicit Aligned(size_t n) : v(n + 16 / sizeof(T) + 1) {}
-  T* p() { return (T*)(((uintptr_t)v.data() + 15) & ~(uintptr_t)15); }
-};
+#include "../emul_support.hpp"
 
 extern "C" {
 // signed digits of one 32-byte scalar after the reduction mod 8l: W = ceil(255 / c) values into digits[]; returns W

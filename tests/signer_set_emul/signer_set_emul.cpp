@@ -18,79 +18,33 @@
 #include <vector>
 #include "../../babyjubjub-rs_amd/csrc/signer_set.hpp"
 #include "../../babyjubjub-rs_amd/csrc/bjj_constants.inc"
-using namespace bjj;
-static const Consts K = {
-    BJJ_K_A, BJJ_K_D, BJJ_K_F, BJJ_K_FINV_PLAIN, BJJ_K_FINV, BJJ_K_L_R1, BJJ_K_L_R2, BJJ_K_DP, BJJ_K_D2P, BJJ_K_DPINV, BJJ_K_B8X, BJJ_K_B8Y, BJJ_K_TS_G, BJJ_K_HALFQ,
-    BJJ_K_ORDER, BJJ_K_ORDER2, BJJ_K_ORDER4, BJJ_K_L, BJJ_K_L2, BJJ_K_L4,
-    BJJ_K_POSEIDON_CF, BJJ_K_POSEIDON_KP, BJJ_K_POSEIDON_SP, BJJ_K_POSEIDON_AL, BJJ_K_POSEIDON_M, BJJ_K_POSEIDON_CAB,
-    BJJ_K_TS_NEG, BJJ_K_TS_HALF, BJJ_K_TS_HASH};
-
-struct Words { alignas(16) u32 w[8]; };
-static bool parse_hex(const char* s, Words& out) {
-  const size_t len = strlen(s);
-  if (len == 0 || len > 64) return false;
-  memset(out.w, 0, sizeof(out.w));
-  for (size_t i = 0; i < len; i++) {
-    const char c = s[len - 1 - i];
-    const int v = c >= '0' && c <= '9' ? c - '0' : c >= 'a' && c <= 'f' ? c - 'a' + 10 : -1;
-    if (v < 0) return false;
-    out.w[i / 8] |= (u32)v << (4 * (i % 8));
-  }
-  return true;
-}
-static bool read_words(Words* out, size_t count) {
-  char tok[80];
-  for (size_t i = 0; i < count; i++)
-    if (scanf("%79s", tok) != 1 || !parse_hex(tok, out[i])) return false;
-  return true;
-}
-static bool read_header(const char* name, size_t& count) {
-  char tok[80];
-  return scanf("%79s %zu", tok, &count) == 2 && !strcmp(tok, name) && count <= 100000;
-}
-static u32* aligned(std::vector<u32>& v) { return (u32*)(((uintptr_t)v.data() + 15) & ~(uintptr_t)15); }
-
-// GatherPerLane that knows the extent of the two tables an item reads: a slot past the end of the table in use ends the program
-struct GatherBounded {
-  struct Pending { Niels e; };
-  static constexpr int kBuffers = 2;
-  const u32* table;
-  const u32 *t0, *t1;
-  size_t n0, n1;
-  static int wave_max(int v) { return v; }
-  void issue(size_t slot, Pending& p, int) const {
-    const size_t limit = table == t0 ? n0 : table == t1 ? n1 : 0;
-    if (slot >= limit) { fprintf(stderr, "gather out of bounds: slot %zu of %zu\n", slot, limit); abort(); }
-    p.e = load_niels(table + slot * NIELS_WORDS);
-  }
-  Niels finish(Pending& p, int) const { return p.e; }
-};
+#include "../emul_support.hpp"
 
 struct SetTable {
   int W = 0, nwin = 0;
   size_t k = 0, eps = 0;
-  std::vector<u32> tv, bv;
+  Aligned<u32> tv, bv;
   const u32* keys = nullptr;
   // thread by thread what build_signer_set launches: k * nwin window bases, then every chain
   void build(const u32* keys_, size_t k_, int W_, u32 chain) {
     keys = keys_; k = k_; W = W_; nwin = base_nwin(W); eps = (size_t)set_entries_per_signer(W);
     if (!set_slots_fit(k, W)) abort();
-    tv.assign(k * eps * NIELS_WORDS + 4, 0xA5A5A5A5u);
-    bv.assign(k * (size_t)nwin * NIELS_WORDS + 4, 0);
-    for (u64 t = 0; t < k * (u64)nwin; t++) set_window_base(aligned(bv), keys, t, W, nwin, K);
+    tv = Aligned<u32>(k * eps * NIELS_WORDS, 0xA5A5A5A5u);
+    bv = Aligned<u32>(k * (size_t)nwin * NIELS_WORDS);
+    for (u64 t = 0; t < k * (u64)nwin; t++) set_window_base(bv.p(), keys, t, W, nwin, K);
     const u64 cpw = (fixed_stride(W) + chain - 1) / chain;
-    for (u64 t = 0; t < k * (u64)nwin * cpw; t++) set_fill_chain(aligned(tv), aligned(bv), t, W, nwin, chain, K);
+    for (u64 t = 0; t < k * (u64)nwin * cpw; t++) set_fill_chain(tv.p(), bv.p(), t, W, nwin, chain, K);
   }
   unsigned long long check() {
     unsigned long long bad = 0;
-    for (u64 e = 0; e < k * eps; e++) bad += (unsigned long long)set_check_entry(aligned(tv), aligned(bv), keys, e, W, nwin, K);
+    for (u64 e = 0; e < k * eps; e++) bad += (unsigned long long)set_check_entry(tv.p(), bv.p(), keys, e, W, nwin, K);
     return bad;
   }
   // third word of entry (window j, digit 1) of signer s: 2x'y in window 0, 2D'x'y elsewhere
   bool tform_as_documented(size_t s) {
     bool ok = true;
     for (int j = 0; j < 2; j++) {
-      const Niels e = load_niels(aligned(tv) + (s * eps + (size_t)j * fixed_stride(W) + 1) * NIELS_WORDS);
+      const Niels e = load_niels(tv.p() + (s * eps + (size_t)j * fixed_stride(W) + 1) * NIELS_WORDS);
       const Fr dsq = fr_sub(fr_sqr(e.ypx), fr_sqr(e.ymx));
       const bool plain = fr_eq(dsq, fr_dbl(e.t2d)), withd = fr_eq(fr_mul(dsq, K.DP), fr_dbl(e.t2d));
       ok = ok && (j == 0 ? plain : withd);
@@ -108,8 +62,8 @@ int main() {
   std::vector<Words> items(5 * ni + 1);
   if (!read_words(items.data(), 5 * ni)) { fprintf(stderr, "bad item\n"); return 2; }
 
-  std::vector<u32> keyv(nk * SET_KEY_WORDS + 4, 0);
-  u32* keys = aligned(keyv);
+  Aligned<u32> keyv(nk * SET_KEY_WORDS);
+  u32* keys = keyv.p();
   for (size_t j = 0; j < nk; j++) {
     u32 xy[16];
     memcpy(xy, kxy[2 * j].w, 32); memcpy(xy + 8, kxy[2 * j + 1].w, 32);
@@ -120,28 +74,20 @@ int main() {
   SetTable T[2];
   T[0].build(keys, nk, 4, 3);
   T[1].build(keys, nk, 5, 8);
-  // the context's B8 table, as tests/signer_emul builds it
-  const int bw = 4, bnwin = fixed_nwin(bw);
-  const size_t bstride = fixed_stride(bw);
-  std::vector<u32> b8t(bstride * (size_t)bnwin * NIELS_WORDS + 4, 0), b8b((size_t)bnwin * NIELS_WORDS + 4, 0);
-  for (int j = 0; j < bnwin; j++) store_niels(aligned(b8b) + (size_t)j * NIELS_WORDS, base_table_entry(K.B8X, K.B8Y, 1u, j, bw, K));
-  for (int j = 0; j < bnwin; j++)
-    fixed_table_chain(aligned(b8t), load_niels(aligned(b8b) + (size_t)j * NIELS_WORDS), (size_t)j * bstride, 0u, (u32)bstride, bw, K);
-  unsigned long long b8bad = 0;
-  for (int j = 0; j < bnwin; j++)
-    for (size_t d = 0; d < bstride; d++) b8bad += (unsigned long long)base_table_check_slot(aligned(b8t), aligned(b8b), j, (u32)d, bw, bnwin, K.B8X, K.B8Y, K);
+  HostTable b8;   // the context's B8 table, one chain per window
+  b8.build(K.B8X, K.B8Y, 4, true, (u32)fixed_stride(4));
   for (int t = 0; t < 2; t++) printf("check %d %llu\n", t, T[t].check());
-  printf("check 2 %llu\n", b8bad);
+  printf("check 2 %llu\n", b8.check());
   for (int t = 0; t < 2; t++)
     for (size_t s = 0; s < nk; s++) printf("tform %d %zu %d\n", T[t].W, s, T[t].tform_as_documented(s) ? 1 : 0);
 
   for (int t = 0; t < 2; t++) {
     SetArgs A;
     memset(&A, 0, sizeof(A));
-    A.T.table = aligned(T[t].tv); A.T.W = T[t].W; A.T.nwin = T[t].nwin; A.T.mod_l = 0;
-    A.L.table = aligned(b8t); A.L.W = bw; A.L.nwin = bnwin; A.L.mod_l = 1;
+    A.T.table = T[t].tv.p(); A.T.W = T[t].W; A.T.nwin = T[t].nwin; A.T.mod_l = 0;
+    A.L = b8.desc();
     A.keys = keys; A.k = (u32)nk; A.eps = (u32)T[t].eps;
-    const GatherBounded g = {A.T.table, A.T.table, A.L.table, nk * T[t].eps, bstride * (size_t)bnwin};
+    const GatherBounded<2> g = {A.T.table, {{A.T.table, nk * T[t].eps}, {A.L.table, b8.slots()}}};
     for (size_t i = 0; i < ni; i++) {
       const Words* it = &items[5 * i];   // idx, then rx, ry read as ONE 64-byte record
       alignas(16) u32 r[16];

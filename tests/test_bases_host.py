@@ -4,11 +4,11 @@ order 8l, at W = 4, 5 and 12, for the order-2 point (0, -1) at W = 4 and for B8 
 generalised induction check, and every result for t = 1, 2, 3 bases is the oracle's: mul_var_base per term, folded with point_add.
 The same program runs once more built with -fsanitize=address,undefined, directly (no preload)."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostbuild
 from bases_cases import directed, random_scalars
 from conftest import ROOT, ints, pack, unpack
 
@@ -16,18 +16,9 @@ Q = 2188824287183927522224640574525727508854836440041603434369820418657580849561
 B8 = (5299619240641551281634865583518297030282874472190772894086521144482721001553,
       16950150798460657717958625567821834550301663161624707787222815936182638968203)
 SRC = os.path.join(ROOT, "tests", "bases_emul", "bases_emul.cpp")
-DEPS = [SRC] + [os.path.join(ROOT, "babyjubjub-rs_amd", "csrc", f)
-                for f in ("fr.hpp", "fr_mul_columns.inc", "curve.hpp", "poseidon.hpp", "bjj_device.hpp", "bases.hpp", "bjj_constants.inc")]
 # the cases bases_emul.cpp runs: name -> its tables; the scalar of base j for item i is S[(i + 7 j) % count]
 CASES = {"p4": "P", "p5": "P", "p12": "P", "two4": "2", "b8": "B", "p4+p12": "PP", "b8+p5": "BP", "two4+p4": "2P", "p12+b8": "PB",
          "p12+b8+two4": "PB2", "p4+p4+p5": "PPP"}
-
-
-def _build(exe, san):
-    if os.path.exists(exe) and all(os.path.getmtime(exe) >= os.path.getmtime(d) for d in DEPS):
-        return None
-    extra = ["-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"] if san else ["-O2"]
-    return subprocess.run(["g++", "-g", "-std=c++17"] + extra + ["-o", exe, SRC], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
 
 
 @pytest.fixture(scope="module")
@@ -127,24 +118,9 @@ def test_signed_recoding_fits_the_windows_of_every_width(W):
 
 
 def test_tables_and_results_match_the_oracle(inputs, expected, tmp_path):
-    exe = os.path.join(ROOT, "tests", "bases_emul", "bases_emul")
-    c = _build(exe, False)
-    assert c is None or c.returncode == 0, c.stdout
-    r = subprocess.run([exe], input=inputs[2], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-3000:]
-    _check_output(r.stdout, inputs, expected)
+    _check_output(hostbuild.run(hostbuild.program("bases_emul", SRC), inputs[2]), inputs, expected)
 
 
 def test_the_same_program_under_asan_and_ubsan(inputs, expected):
-    for rt in ("libasan.so", "libubsan.so"):     # asked of the toolchain BEFORE the build: a build that fails is a failure
-        path = subprocess.run(["g++", "-print-file-name=" + rt], stdout=subprocess.PIPE, text=True).stdout.strip()
-        if not os.path.isabs(path) or not os.path.exists(path):
-            pytest.skip("no %s in this toolchain" % rt)
-    exe = os.path.join(ROOT, "tests", "bases_emul", "bases_emul_san")
-    c = _build(exe, True)
-    assert c is None or c.returncode == 0, c.stdout
-    r = subprocess.run([exe], input=inputs[2], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=1200,
-                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1"))
-    assert r.returncode == 0, r.stdout[-3000:]
-    assert "AddressSanitizer" not in r.stdout and "runtime error" not in r.stdout, r.stdout[-3000:]
-    _check_output(r.stdout, inputs, expected)
+    hostbuild.need_sanitizer_runtimes()          # BEFORE the build: a build that fails is a failure
+    _check_output(hostbuild.run_sanitized(hostbuild.program("bases_emul_san", SRC, san=True), inputs[2]), inputs, expected)

@@ -5,17 +5,14 @@ bjj_k_mul_common in both forms with the point and the subgroup epilogue -- the b
 import ctypes
 import os
 import random
-import subprocess
 
 import pytest
 
-from conftest import ROOT, _sh
+import hostbuild
+from conftest import ROOT
 from test_msm_host import L, ORDER8, le
 
-CSRC = os.path.join(ROOT, "babyjubjub-rs_amd", "csrc")
 EMUL_DIR = os.path.join(ROOT, "tests", "common_scalar_emul")
-EMUL_SRCS = [os.path.join(EMUL_DIR, "common_scalar_emul.cpp")] + [os.path.join(CSRC, f) for f in (
-    "fr.hpp", "curve.hpp", "poseidon.hpp", "bjj_device.hpp", "common_scalar.hpp", "bjj_constants.inc")]
 NAF, TABLE = 0, 1
 FORMS = (NAF, TABLE)
 FIXED_SCALARS = [0, 1, 2, 8, L - 1, L, L + 1, ORDER8 - 1, ORDER8, ORDER8 + 1, 1 << 253, (1 << 254) - 1, (1 << 256) - 1,
@@ -29,10 +26,7 @@ def all_scalars():
 
 @pytest.fixture(scope="module")
 def emul():
-    so = os.path.join(EMUL_DIR, "libcommon_scalar_emul.so")
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in EMUL_SRCS):
-        _sh(["g++", "-O2", "-g", "-std=c++17", "-shared", "-fPIC", "-o", so, EMUL_SRCS[0]], EMUL_DIR)
-    lib = ctypes.CDLL(so)
+    lib = ctypes.CDLL(hostbuild.shared("libcommon_scalar_emul.so", os.path.join(EMUL_DIR, "common_scalar_emul.cpp")))
     lib.cs_emul_recode.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_byte), ctypes.POINTER(ctypes.c_int)]
     lib.cs_emul_choose.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
     lib.cs_emul_mul.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_int, ctypes.c_char_p,
@@ -175,15 +169,8 @@ def test_the_subgroup_epilogue(emul, pyoracle, points, form):
 
 
 # ---- the same bodies under the sanitizers -----------------------------------------------------------------------------------------
-def test_the_mixed_case_under_asan_and_ubsan(tmp_path):
+def test_the_mixed_case_under_asan_and_ubsan():
     """a stand-alone program: the harness and its driver compiled with -fsanitize=address,undefined, run directly"""
-    exe = str(tmp_path / "common_scalar_emul_san")
-    c = subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe,
-                        os.path.join(EMUL_DIR, "common_scalar_emul_main.cpp")], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    if c.returncode != 0 and "sanitize" in c.stdout:
-        pytest.skip("sanitizer runtime not available: " + c.stdout[-300:])
-    assert c.returncode == 0, c.stdout[-3000:]
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600,
-                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1"))
-    assert r.returncode == 0 and "common_scalar ok" in r.stdout, r.stdout[-3000:]
-    assert "AddressSanitizer" not in r.stdout and "runtime error" not in r.stdout, r.stdout[-3000:]
+    hostbuild.need_sanitizer_runtimes()
+    out = hostbuild.run_sanitized(hostbuild.program("common_scalar_emul_san", os.path.join(EMUL_DIR, "common_scalar_emul_main.cpp"), san=True), timeout=600)
+    assert "common_scalar ok" in out, out[-3000:]

@@ -15,12 +15,12 @@ every other error is an ordinary failing assertion of the op's test."""
 import ctypes
 import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
 
 import curve_ref as cr
+import hostbuild
 from conftest import ROOT
 
 R_MOD = cr.R_MOD
@@ -28,17 +28,9 @@ N_RANDOM = 1 << 12
 
 
 def build_clib(layout):
-    """tests/emul/libbjj_emul_curve_ops_l<layout>.so, rebuilt when the dispatcher, its source or an included product header is newer"""
-    d = os.path.join(ROOT, "tests", "emul")
-    so = os.path.join(d, "libbjj_emul_curve_ops_l%d.so" % layout)
-    srcs = [os.path.join(d, "emul_curve_ops.cpp"), os.path.join(ROOT, "tests", "devfuzz", "curve_ops.hpp")] + [
-        os.path.join(ROOT, "babyjubjub-rs_amd", "csrc", f)
-        for f in ("fr.hpp", "curve.hpp", "poseidon.hpp", "bjj_device.hpp", "bjj_constants.inc")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        r = subprocess.run(["g++", "-O2", "-g", "-std=c++17", "-shared", "-fPIC", "-DBJJ_PNIELS_LAYOUT=%d" % layout, "-o", so, srcs[0]],
-                           stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        assert r.returncode == 0, r.stdout
-    lib = ctypes.CDLL(so)
+    """the dispatcher of tests/devfuzz/curve_ops.hpp built for the CPU, per per-lane table layout"""
+    lib = ctypes.CDLL(hostbuild.shared("libbjj_emul_curve_ops_l%d.so" % layout, os.path.join(ROOT, "tests", "emul", "emul_curve_ops.cpp"),
+                                       defines=("BJJ_PNIELS_LAYOUT=%d" % layout,)))
     assert lib.emul_curve_layout() == layout
     for op, code in cr.OPS.items():
         assert tuple(lib.emul_curve_words(code, k) for k in range(4)) == cr.WIDTHS[op], op

@@ -11,21 +11,13 @@ import subprocess
 
 import pytest
 
+import hostbuild
 import dlog_cases as dc
 import dlog_ref as dr
 from conftest import ROOT, ints
 
 SRC = os.path.join(ROOT, "tests", "dlog_emul", "dlog_emul.cpp")
-DEPS = [SRC] + [os.path.join(ROOT, "babyjubjub-rs_amd", "csrc", f)
-                for f in ("fr.hpp", "fr_mul_columns.inc", "curve.hpp", "bjj_device.hpp", "dlog.hpp", "bjj_constants.inc")]
 TABLES = [("b8", 4), ("b8", 6), ("order_8l", 4), ("order_8l", 6)]
-
-
-def _build(exe, san):
-    if os.path.exists(exe) and all(os.path.getmtime(exe) >= os.path.getmtime(d) for d in DEPS):
-        return None
-    extra = ["-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"] if san else ["-O2"]
-    return subprocess.run(["g++", "-g", "-std=c++17"] + extra + ["-o", exe, SRC], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
 
 
 @pytest.fixture(scope="module")
@@ -101,38 +93,22 @@ def _check_output(out, inp, b):
 
 @pytest.mark.parametrize("name,b", TABLES)
 def test_results_match_the_python_oracle(inputs, name, b):
-    exe = os.path.join(ROOT, "tests", "dlog_emul", "dlog_emul")
-    c = _build(exe, False)
-    assert c is None or c.returncode == 0, c.stdout
-    r = subprocess.run([exe], input=inputs[(name, b)]["text"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-3000:]
-    _check_output(r.stdout, inputs[(name, b)], b)
+    _check_output(hostbuild.run(hostbuild.program("dlog_emul", SRC), inputs[(name, b)]["text"]), inputs[(name, b)], b)
 
 
 def test_a_base_of_small_order_is_reported(golden):
-    exe = os.path.join(ROOT, "tests", "dlog_emul", "dlog_emul")
-    c = _build(exe, False)
-    assert c is None or c.returncode == 0, c.stdout
+    exe = hostbuild.program("dlog_emul", SRC)
     for t in golden["gpu_expected"]["torsion_points"]:                  # the identity and the seven other points of order <= 8
         x, y = ints(t)
-        r = subprocess.run([exe], input="G %x %x\nT 4 3\nR 1 4\nI 0\n" % (x, y), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=60)
-        assert r.returncode == 0 and r.stdout.split("\n")[0] == "small 1", (t, r.stdout, r.stderr)
+        out = hostbuild.run(exe, "G %x %x\nT 4 3\nR 1 4\nI 0\n" % (x, y), timeout=60)
+        assert out.split("\n")[0] == "small 1", (t, out)
 
 
 @pytest.mark.parametrize("name,b", [("b8", 4), ("order_8l", 6)])
 def test_the_same_program_under_asan_and_ubsan(inputs, name, b):
-    for rt in ("libasan.so", "libubsan.so"):     # asked of the toolchain BEFORE the build: a build that fails is a failure
-        path = subprocess.run(["g++", "-print-file-name=" + rt], stdout=subprocess.PIPE, text=True).stdout.strip()
-        if not os.path.isabs(path) or not os.path.exists(path):
-            pytest.skip("no %s in this toolchain" % rt)
-    exe = os.path.join(ROOT, "tests", "dlog_emul", "dlog_emul_san")
-    c = _build(exe, True)
-    assert c is None or c.returncode == 0, c.stdout
-    r = subprocess.run([exe], input=inputs[(name, b)]["text"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=1200,
-                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1"))
-    assert r.returncode == 0, r.stdout[-3000:]
-    assert "AddressSanitizer" not in r.stdout and "runtime error" not in r.stdout, r.stdout[-3000:]
-    _check_output(r.stdout, inputs[(name, b)], b)
+    hostbuild.need_sanitizer_runtimes()          # BEFORE the build: a build that fails is a failure
+    out = hostbuild.run_sanitized(hostbuild.program("dlog_emul_san", SRC, san=True), inputs[(name, b)]["text"])
+    _check_output(out, inputs[(name, b)], b)
 
 
 # ---- constructed false hits and a wrapped probe run: the plain-integer model tests/dlog_ref.py against the source ---------------------
@@ -140,13 +116,9 @@ DIRECTED = [("b8", 4, 12), ("b8", 8, 14), ("order_8l", 6, 12)]
 
 
 def _emul(text):
-    exe = os.path.join(ROOT, "tests", "dlog_emul", "dlog_emul")
-    c = _build(exe, False)
-    assert c is None or c.returncode == 0, c.stdout
-    r = subprocess.run([exe], input=text, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-3000:]
+    out = hostbuild.run(hostbuild.program("dlog_emul", SRC), text)
     f = {"r": {}, "s": {}, "check": {}, "rejected": {}, "slots": {}}
-    for line in r.stdout.split("\n"):
+    for line in out.split("\n"):
         w = line.split()
         if not w:
             continue

@@ -5,18 +5,15 @@ under AddressSanitizer and UndefinedBehaviorSanitizer."""
 import ctypes
 import os
 import random
-import subprocess
 
 import pytest
 
 import bases_cases
 from bases_cases import L, ORDER8
-from conftest import ROOT, _sh
+import hostbuild
+from conftest import ROOT
 
-CSRC = os.path.join(ROOT, "babyjubjub-rs_amd", "csrc")
 EMUL_DIR = os.path.join(ROOT, "tests", "elgamal_emul")
-EMUL_SRCS = [os.path.join(EMUL_DIR, "elgamal_emul.cpp")] + [os.path.join(CSRC, f) for f in (
-    "fr.hpp", "curve.hpp", "poseidon.hpp", "bjj_device.hpp", "bases.hpp", "elgamal.hpp", "bjj_constants.inc")]
 WIDTHS = (4, 5, 13, 16)
 M64 = (1 << 64) - 1
 
@@ -71,10 +68,7 @@ def test_the_short_recoding_of_m_is_exact_and_its_top_digit_is_not_negative():
 # ---- the harness --------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def emul():
-    so = os.path.join(EMUL_DIR, "libelgamal_emul.so")
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in EMUL_SRCS):
-        _sh(["g++", "-O2", "-g", "-std=c++17", "-shared", "-fPIC", "-o", so, EMUL_SRCS[0]], EMUL_DIR)
-    lib = ctypes.CDLL(so)
+    lib = ctypes.CDLL(hostbuild.shared("libelgamal_emul.so", os.path.join(EMUL_DIR, "elgamal_emul.cpp")))
     lib.eg_emul_table.argtypes = [ctypes.c_char_p, ctypes.c_int]
     lib.eg_emul_digits.argtypes = [ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_longlong)]
     lib.eg_emul_digits.restype = None
@@ -226,13 +220,7 @@ def test_the_harness_rejects_what_the_library_rejects(emul, world):
 
 
 # ---- the same body under the sanitizers ---------------------------------------------------------------------------------------------
-def test_the_mixed_case_under_asan_and_ubsan(tmp_path):
+def test_the_mixed_case_under_asan_and_ubsan():
     """a stand-alone program: the harness and its driver compiled with -fsanitize=address,undefined, run directly"""
-    exe = str(tmp_path / "elgamal_emul_san")
-    c = subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe,
-                        os.path.join(EMUL_DIR, "elgamal_emul_main.cpp")], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert c.returncode == 0, c.stdout[-3000:]
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600,
-                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1"))
-    assert r.returncode == 0 and "elgamal ok" in r.stdout, r.stdout[-3000:]
-    assert "AddressSanitizer" not in r.stdout and "runtime error" not in r.stdout, r.stdout[-3000:]
+    out = hostbuild.run_sanitized(hostbuild.program("elgamal_emul_san", os.path.join(EMUL_DIR, "elgamal_emul_main.cpp"), san=True), timeout=600)
+    assert "elgamal ok" in out, out[-3000:]

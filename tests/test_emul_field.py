@@ -4,10 +4,10 @@ tests/emul/emul_fr.cpp with limb/column/value-bound assertions on, against Pytho
 import ctypes
 import os
 import random
-import subprocess
 
 import pytest
 
+import hostbuild
 from conftest import ROOT, le32
 
 Q = 21888242871839275222246405745257275088548364400416034343698204186575808495617
@@ -15,15 +15,7 @@ Q = 2188824287183927522224640574525727508854836440041603434369820418657580849561
 
 @pytest.fixture(scope="module")
 def frlib():
-    d = os.path.join(ROOT, "tests", "emul")
-    so = os.path.join(d, "libbjj_emul_fr.so")
-    srcs = [os.path.join(d, "emul_fr.cpp"), os.path.join(ROOT, "babyjubjub-rs_amd", "csrc", "fr.hpp")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        r = subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-shared", "-fPIC", "-o", so, srcs[0]],
-                           stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        assert r.returncode == 0, r.stdout
-    return ctypes.CDLL(so)
-
+    return ctypes.CDLL(hostbuild.shared("libbjj_emul_fr.so", os.path.join(ROOT, "tests", "emul", "emul_fr.cpp"), opt="-O1"))
 
 def _vals(rnd, n):
     edge = [0, 1, 2, Q - 1, Q - 2, (1 << 256) - 1, Q, Q + 1, 1 << 255, (1 << 29) - 1, 1 << 29, (1 << 232) - 1]

@@ -7,11 +7,11 @@ eight v_mad_i64_i32 of a limb as one inline-asm statement -- never runs here: it
 set (tests/divstep_ref.py), by tests/test_gpu_devfuzz.py::test_k1_inversion_core_on_device and ::test_block_invert_directed_lanes."""
 import ctypes
 import os
-import subprocess
 
 import pytest
 
 import divstep_ref as ds
+import hostbuild
 from conftest import ROOT, le32
 
 Q = 21888242871839275222246405745257275088548364400416034343698204186575808495617   # r
@@ -20,14 +20,7 @@ R = 1 << 261
 
 @pytest.fixture(scope="module")
 def invlib():
-    d = os.path.join(ROOT, "tests", "emul")
-    so = os.path.join(d, "libbjj_emul_inv_k1.so")
-    srcs = [os.path.join(d, "emul_inv_k1.cpp"), os.path.join(ROOT, "babyjubjub-rs_amd", "csrc", "fr.hpp")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        r = subprocess.run(["g++", "-O2", "-g", "-std=c++17", "-shared", "-fPIC", "-pthread", "-o", so, srcs[0]],
-                           stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        assert r.returncode == 0, r.stdout
-    lib = ctypes.CDLL(so)
+    lib = ctypes.CDLL(hostbuild.shared("libbjj_emul_inv_k1.so", os.path.join(ROOT, "tests", "emul", "emul_inv_k1.cpp"), extra=("-pthread",)))
     lib.emul_inv_k1_splitmix.restype = ctypes.c_long
     lib.emul_inv_k1_splitmix.argtypes = [ctypes.c_ulonglong, ctypes.c_long, ctypes.c_char_p]
     return lib

@@ -13,12 +13,12 @@ violation; every other error is an ordinary failing assertion of the op's test."
 import ctypes
 import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
 
 import field_ref as fr
+import hostbuild
 from conftest import ROOT
 
 N_RANDOM = 1 << 14
@@ -26,17 +26,8 @@ N_RANDOM = 1 << 14
 
 @pytest.fixture(scope="module")
 def flib():
-    """tests/emul/libbjj_emul_field_ops.so, rebuilt when the dispatcher, its source or an included product header is newer"""
-    d = os.path.join(ROOT, "tests", "emul")
-    so = os.path.join(d, "libbjj_emul_field_ops.so")
-    srcs = [os.path.join(d, "emul_field_ops.cpp"), os.path.join(ROOT, "tests", "devfuzz", "field_ops.hpp")] + [
-        os.path.join(ROOT, "babyjubjub-rs_amd", "csrc", f)
-        for f in ("fr.hpp", "curve.hpp", "poseidon.hpp", "bjj_device.hpp", "bjj_constants.inc")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        r = subprocess.run(["g++", "-O2", "-g", "-std=c++17", "-shared", "-fPIC", "-o", so, srcs[0]],
-                           stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        assert r.returncode == 0, r.stdout
-    lib = ctypes.CDLL(so)
+    """the dispatcher of tests/devfuzz/field_ops.hpp built for the CPU"""
+    lib = ctypes.CDLL(hostbuild.shared("libbjj_emul_field_ops.so", os.path.join(ROOT, "tests", "emul", "emul_field_ops.cpp")))
     for op, code in fr.OPS.items():
         assert tuple(lib.emul_field_words(code, k) for k in range(3)) == fr.WIDTHS[op], op
     return lib

@@ -14,6 +14,7 @@ import os
 import random
 import subprocess
 
+import hostbuild
 from test_k1_weak_mod_l_host import L, _digits
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -71,12 +72,8 @@ def _directed(W):
 
 
 def test_sign_carry_equals_fixed_base_mul_for_every_width(tmp_path):
-    exe = str(tmp_path / "k1_sign_carry_san")
-    r = subprocess.run(["g++", "-O2", "-g", "-std=c++17", "-DBJJ_DEBUG_BOUNDS", "-fsanitize=address,undefined",
-                        "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-o", exe,
-                        os.path.join(ROOT, "tests", "emul", "k1_sign_carry_main.cpp")],
-                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
+    exe = hostbuild.program("k1_sign_carry_san", os.path.join(ROOT, "tests", "emul", "k1_sign_carry_main.cpp"), san=True, opt="-O2",
+                            defines=("BJJ_DEBUG_BOUNDS",))
     rnd = random.Random(0x51C7)
     lines = {W: [(W, v) for v in _directed(W)] for W in WIDTHS}
     for i in range(RANDOM):

@@ -6,7 +6,8 @@ stand-alone program (tests/emul/weak_mod_l_main.cpp) built with AddressSanitizer
 Python integers."""
 import os
 import random
-import subprocess
+
+import hostbuild
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 L = 2736030358979909402780800718157159386076813972158567259200215660948447373041
@@ -38,18 +39,12 @@ def _digits(s, W):
     return out, carry
 
 
-def test_weak_mod_l_contract_and_digits_for_every_width(tmp_path):
-    exe = str(tmp_path / "weak_mod_l_san")
-    r = subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                        "-fno-omit-frame-pointer", "-o", exe, os.path.join(ROOT, "tests", "emul", "weak_mod_l_main.cpp")],
-                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
+def test_weak_mod_l_contract_and_digits_for_every_width():
+    exe = hostbuild.program("weak_mod_l_san", os.path.join(ROOT, "tests", "emul", "weak_mod_l_main.cpp"), san=True)
     plain, edges = _inputs()
     assert len(plain) == 256 * 66 and len(edges) >= 5 * (len(ESTIMATES) - 2)
     text = "".join("%064x\n" % v for v in plain) + "".join("D %064x\n" % v for v in edges)
-    r = subprocess.run([exe], input=text, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
-    assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
-    lines = r.stdout.split("\n")
+    lines = hostbuild.run_sanitized(exe, text).split("\n")
     pos = 0
     worst = 0
     for k, v in enumerate(plain + edges):

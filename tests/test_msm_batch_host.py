@@ -10,7 +10,8 @@ import sys
 
 import pytest
 
-from conftest import ROOT, _sh
+import hostbuild
+from conftest import ROOT
 from test_msm_host import KINDS, _inputs, fold, le
 
 HEADER = os.path.join(ROOT, "include", "bjj_hip_msm_batch.h")
@@ -19,14 +20,7 @@ OFFSETS_MIXED = [0, 1, 1, 2, 64, 65, 129, 300]
 
 @pytest.fixture(scope="module")
 def emul():
-    d = os.path.join(ROOT, "tests", "msm_batch_emul")
-    so = os.path.join(d, "libmsm_batch_emul.so")
-    srcs = [os.path.join(d, "msm_batch_emul.cpp")] + [os.path.join(ROOT, "babyjubjub-rs_amd", "csrc", f)
-                                                      for f in ("fr.hpp", "curve.hpp", "poseidon.hpp", "bjj_device.hpp", "msm.hpp",
-                                                                "bjj_constants.inc")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        _sh(["g++", "-O2", "-g", "-std=c++17", "-shared", "-fPIC", "-o", so, srcs[0]], d)
-    lib = ctypes.CDLL(so)
+    lib = ctypes.CDLL(hostbuild.shared("libmsm_batch_emul.so", os.path.join(ROOT, "tests", "msm_batch_emul", "msm_batch_emul.cpp")))
     lib.msm_batch_emul_run.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_ulonglong),
                                        ctypes.c_size_t, ctypes.c_int, ctypes.c_char_p, ctypes.POINTER(ctypes.c_longlong)]
     lib.msm_batch_emul_segment.argtypes = [ctypes.POINTER(ctypes.c_ulonglong), ctypes.c_size_t, ctypes.c_ulonglong]

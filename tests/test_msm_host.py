@@ -11,7 +11,8 @@ import sys
 
 import pytest
 
-from conftest import ROOT, _sh
+import hostbuild
+from conftest import ROOT
 
 L = 2736030358979909402780800718157159386076813972158567259200215660948447373041
 ORDER8 = 8 * L
@@ -21,14 +22,7 @@ EDGE_SCALARS = [0, 1, 2, ORDER8 - 1, ORDER8, ORDER8 + 1, 2 * ORDER8 - 1, (1 << 2
 
 @pytest.fixture(scope="module")
 def msm_emul():
-    d = os.path.join(ROOT, "tests", "msm_emul")
-    so = os.path.join(d, "libmsm_emul.so")
-    srcs = [os.path.join(d, "msm_emul.cpp")] + [os.path.join(ROOT, "babyjubjub-rs_amd", "csrc", f)
-                                                for f in ("fr.hpp", "curve.hpp", "poseidon.hpp", "bjj_device.hpp", "msm.hpp",
-                                                          "bjj_constants.inc")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        _sh(["g++", "-O2", "-g", "-std=c++17", "-shared", "-fPIC", "-o", so, srcs[0]], d)
-    lib = ctypes.CDLL(so)
+    lib = ctypes.CDLL(hostbuild.shared("libmsm_emul.so", os.path.join(ROOT, "tests", "msm_emul", "msm_emul.cpp")))
     lib.msm_emul_run.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_char_p,
                                  ctypes.POINTER(ctypes.c_longlong)]
     lib.msm_emul_digits.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]

@@ -5,10 +5,10 @@ schedule (pipe_model.py), with the layout computed here, and with the invariants
 import itertools
 import json
 import os
-import subprocess
 
 import pytest
 
+import hostbuild
 from conftest import ROOT
 from pipe_model import schedule
 
@@ -33,23 +33,15 @@ def _line(c):
 
 
 @pytest.fixture(scope="module")
-def emul(tmp_path_factory):
+def emul():
     """run(lines) -> the program's output lines; the sanitizers abort on the first finding"""
-    exe = str(tmp_path_factory.mktemp("pipe_plan") / "emul_pipe_plan")
-    src = os.path.join(ROOT, "tests", "emul", "emul_pipe_plan.cpp")
-    c = subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe, src],
-                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    if c.returncode != 0 and "sanitize" in c.stdout:
-        pytest.skip("sanitizer runtime not available: " + c.stdout[-300:])
-    assert c.returncode == 0, c.stdout
+    hostbuild.need_sanitizer_runtimes()
+    exe = hostbuild.program("emul_pipe_plan", os.path.join(ROOT, "tests", "emul", "emul_pipe_plan.cpp"), san=True)
 
     def run(lines):
-        r = subprocess.run([exe], input="\n".join(lines) + "\n", stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300,
-                           env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1"))
-        assert r.returncode == 0, r.stdout[-3000:]
-        assert "AddressSanitizer" not in r.stdout and "runtime error" not in r.stdout, r.stdout[-3000:]
-        out = r.stdout.splitlines()
-        assert len(out) == len(lines), r.stdout[-3000:]
+        text = hostbuild.run_sanitized(exe, "\n".join(lines) + "\n", timeout=300)
+        out = text.splitlines()
+        assert len(out) == len(lines), text[-3000:]
         return out
     return run
 

@@ -11,24 +11,20 @@ import sys
 
 import pytest
 
-from conftest import ROOT, _sh
+import hostbuild
+from conftest import ROOT
 from test_msm_batch_host import OFFSETS_MIXED, emul as batch_emul, emul_batch  # noqa: F401  (batch_emul is a fixture)
 from test_msm_host import KINDS, ORDER8, _inputs, le
 
 HEADER = os.path.join(ROOT, "include", "bjj_hip_point_sum.h")
 CSRC = os.path.join(ROOT, "babyjubjub-rs_amd", "csrc")
 EMUL_DIR = os.path.join(ROOT, "tests", "point_sum_emul")
-EMUL_SRCS = [os.path.join(EMUL_DIR, "point_sum_emul.cpp")] + [os.path.join(CSRC, f) for f in (
-    "fr.hpp", "curve.hpp", "poseidon.hpp", "bjj_device.hpp", "msm.hpp", "point_sum.hpp", "bjj_constants.inc")]
 TILES = (8, 16)
 
 
 @pytest.fixture(scope="module")
 def emul():
-    so = os.path.join(EMUL_DIR, "libpoint_sum_emul.so")
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in EMUL_SRCS):
-        _sh(["g++", "-O2", "-g", "-std=c++17", "-shared", "-fPIC", "-o", so, EMUL_SRCS[0]], EMUL_DIR)
-    lib = ctypes.CDLL(so)
+    lib = ctypes.CDLL(hostbuild.shared("libpoint_sum_emul.so", os.path.join(EMUL_DIR, "point_sum_emul.cpp")))
     lib.point_sum_emul_run.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_ulonglong),
                                        ctypes.c_size_t, ctypes.c_int, ctypes.c_char_p, ctypes.POINTER(ctypes.c_longlong)]
     lib.point_sum_emul_segment.argtypes = [ctypes.POINTER(ctypes.c_ulonglong), ctypes.c_size_t, ctypes.c_ulonglong]
@@ -281,15 +277,8 @@ def test_bad_offsets_are_data_in_the_device_form(emul, pool, offsets):
 
 
 # ---- the same bodies under the sanitizers -------------------------------------------------------------------------------------------
-def test_the_mixed_case_under_asan_and_ubsan(tmp_path):
+def test_the_mixed_case_under_asan_and_ubsan():
     """a stand-alone program: the harness and its driver compiled with -fsanitize=address,undefined, run directly"""
-    exe = str(tmp_path / "point_sum_emul_san")
-    c = subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe,
-                        os.path.join(EMUL_DIR, "point_sum_emul_main.cpp")], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    if c.returncode != 0 and "sanitize" in c.stdout:
-        pytest.skip("sanitizer runtime not available: " + c.stdout[-300:])
-    assert c.returncode == 0, c.stdout[-3000:]
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600,
-                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1"))
-    assert r.returncode == 0 and "point_sum ok" in r.stdout, r.stdout[-3000:]
-    assert "AddressSanitizer" not in r.stdout and "runtime error" not in r.stdout, r.stdout[-3000:]
+    hostbuild.need_sanitizer_runtimes()
+    out = hostbuild.run_sanitized(hostbuild.program("point_sum_emul_san", os.path.join(EMUL_DIR, "point_sum_emul_main.cpp"), san=True), timeout=600)
+    assert "point_sum ok" in out, out[-3000:]

@@ -6,28 +6,18 @@ several projective scalings give the same verdict (the homogeneity of PointProje
 occur, and an R that makes the reference's sum z == 0 gives 0.  The same program runs once more built with
 -fsanitize=address,undefined, directly (no preload)."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostbuild
 import signer_cases as sc
 from conftest import ROOT, ints, unpack
 
 Q = sc.Q
 SRC = os.path.join(ROOT, "tests", "signer_emul", "signer_emul.cpp")
-DEPS = [SRC] + [os.path.join(ROOT, "babyjubjub-rs_amd", "csrc", f)
-                for f in ("fr.hpp", "fr_mul_columns.inc", "curve.hpp", "poseidon.hpp", "bjj_device.hpp", "bases.hpp", "signer.hpp",
-                          "bjj_constants.inc")]
 SCALINGS = [2, Q - 1, 0x1234567890abcdef1234567890abcdef1234567890abcdef1234567890abcdef % Q, 3 * Q + 5]   # the last one is >= r: reduced to 5
 KEYS = ("ordinary", "order 8l")
-
-
-def _build(exe, san):
-    if os.path.exists(exe) and all(os.path.getmtime(exe) >= os.path.getmtime(d) for d in DEPS):
-        return None
-    extra = ["-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"] if san else ["-O2"]
-    return subprocess.run(["g++", "-g", "-std=c++17"] + extra + ["-o", exe, SRC], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
 
 
 def _verdict_cases(o, A):
@@ -112,25 +102,11 @@ def _check_output(out, inp):
 
 @pytest.mark.parametrize("key", KEYS)
 def test_verdicts_match_the_python_oracle(inputs, key):
-    exe = os.path.join(ROOT, "tests", "signer_emul", "signer_emul")
-    c = _build(exe, False)
-    assert c is None or c.returncode == 0, c.stdout
-    r = subprocess.run([exe], input=inputs[key]["text"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-3000:]
-    _check_output(r.stdout, inputs[key])
+    _check_output(hostbuild.run(hostbuild.program("signer_emul", SRC), inputs[key]["text"]), inputs[key])
 
 
 def test_the_same_program_under_asan_and_ubsan(inputs):
-    for rt in ("libasan.so", "libubsan.so"):     # asked of the toolchain BEFORE the build: a build that fails is a failure
-        path = subprocess.run(["g++", "-print-file-name=" + rt], stdout=subprocess.PIPE, text=True).stdout.strip()
-        if not os.path.isabs(path) or not os.path.exists(path):
-            pytest.skip("no %s in this toolchain" % rt)
-    exe = os.path.join(ROOT, "tests", "signer_emul", "signer_emul_san")
-    c = _build(exe, True)
-    assert c is None or c.returncode == 0, c.stdout
+    hostbuild.need_sanitizer_runtimes()          # BEFORE the build: a build that fails is a failure
+    exe = hostbuild.program("signer_emul_san", SRC, san=True)
     for key in KEYS:
-        r = subprocess.run([exe], input=inputs[key]["text"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=1200,
-                           env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1"))
-        assert r.returncode == 0, r.stdout[-3000:]
-        assert "AddressSanitizer" not in r.stdout and "runtime error" not in r.stdout, r.stdout[-3000:]
-        _check_output(r.stdout, inputs[key])
+        _check_output(hostbuild.run_sanitized(exe, inputs[key]["text"]), inputs[key])

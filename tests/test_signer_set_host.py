@@ -5,28 +5,18 @@ bodies of the set's build kernels, and a context's B8 table at W = 4.  Every ver
 verify_schnorr for the key the item's index names; an index that is not one of the set gives 3.  The same program runs once more
 built with -fsanitize=address,undefined, directly (no preload)."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostbuild
 import signer_cases as sc
 from conftest import ROOT, ints, unpack
 
 Q = sc.Q
 SRC = os.path.join(ROOT, "tests", "signer_set_emul", "signer_set_emul.cpp")
-DEPS = [SRC] + [os.path.join(ROOT, "babyjubjub-rs_amd", "csrc", f)
-                for f in ("fr.hpp", "fr_mul_columns.inc", "curve.hpp", "poseidon.hpp", "bjj_device.hpp", "bases.hpp", "signer.hpp",
-                          "signer_set.hpp", "bjj_constants.inc")]
 K = 3
 BAD_SIGNER = 3
-
-
-def _build(exe, san):
-    if os.path.exists(exe) and all(os.path.getmtime(exe) >= os.path.getmtime(d) for d in DEPS):
-        return None
-    extra = ["-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"] if san else ["-O2"]
-    return subprocess.run(["g++", "-g", "-std=c++17"] + extra + ["-o", exe, SRC], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
 
 
 @pytest.fixture(scope="module")
@@ -109,24 +99,9 @@ def _check_output(out, inp):
 
 
 def test_verdicts_match_the_python_oracle(inputs):
-    exe = os.path.join(ROOT, "tests", "signer_set_emul", "signer_set_emul")
-    c = _build(exe, False)
-    assert c is None or c.returncode == 0, c.stdout
-    r = subprocess.run([exe], input=inputs["text"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-3000:]
-    _check_output(r.stdout, inputs)
+    _check_output(hostbuild.run(hostbuild.program("signer_set_emul", SRC), inputs["text"]), inputs)
 
 
 def test_the_same_program_under_asan_and_ubsan(inputs):
-    for rt in ("libasan.so", "libubsan.so"):     # asked of the toolchain BEFORE the build: a build that fails is a failure
-        path = subprocess.run(["g++", "-print-file-name=" + rt], stdout=subprocess.PIPE, text=True).stdout.strip()
-        if not os.path.isabs(path) or not os.path.exists(path):
-            pytest.skip("no %s in this toolchain" % rt)
-    exe = os.path.join(ROOT, "tests", "signer_set_emul", "signer_set_emul_san")
-    c = _build(exe, True)
-    assert c is None or c.returncode == 0, c.stdout
-    r = subprocess.run([exe], input=inputs["text"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=1200,
-                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1"))
-    assert r.returncode == 0, r.stdout[-3000:]
-    assert "AddressSanitizer" not in r.stdout and "runtime error" not in r.stdout, r.stdout[-3000:]
-    _check_output(r.stdout, inputs)
+    hostbuild.need_sanitizer_runtimes()          # BEFORE the build: a build that fails is a failure
+    _check_output(hostbuild.run_sanitized(hostbuild.program("signer_set_emul_san", SRC, san=True), inputs["text"]), inputs)
