@@ -71,6 +71,9 @@ BJJ_COMMON_OK, BJJ_COMMON_OFF_CURVE = 1, 2
 # ... and include/bjj_hip_elgamal.h
 ELGAMAL_SYMBOLS = ("bjj_elgamal_encrypt", "bjj_elgamal_encrypt_dev")
 BJJ_ELGAMAL_OK, BJJ_ELGAMAL_OFF_CURVE = 1, 2
+# ... and include/bjj_hip_dleq.h
+DLEQ_SYMBOLS = ("bjj_mul_pair", "bjj_mul_pair_dev", "bjj_dleq_verify", "bjj_dleq_verify_dev", "bjj_dleq_prove", "bjj_dleq_prove_dev")
+BJJ_DLEQ_REJECT, BJJ_DLEQ_OK, BJJ_DLEQ_OFF_CURVE = 0, 1, 2
 
 
 class BjjInfo(ctypes.Structure):
@@ -242,6 +245,12 @@ def load():
     lib.bjj_elgamal_decrypt_dev.argtypes = [vp, vp, vp, vp, vp, sz, ci, vp, vp, vp]
     lib.bjj_elgamal_encrypt.argtypes = [vp, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp]
     lib.bjj_elgamal_encrypt_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp]
+    lib.bjj_mul_pair.argtypes = [vp, vp, vp, vp, vp, vp, sz, vp, vp]
+    lib.bjj_mul_pair_dev.argtypes = [vp, vp, vp, vp, vp, vp, sz, vp, vp, vp]
+    lib.bjj_dleq_verify.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    lib.bjj_dleq_verify_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp]
+    lib.bjj_dleq_prove.argtypes = [vp, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp]
+    lib.bjj_dleq_prove_dev.argtypes = [vp, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp]
     # multi-GPU
     pd = ctypes.POINTER(ctypes.c_double)
     lib.bjj_multi_init.argtypes = [ctypes.POINTER(ci), ci, ci, ctypes.POINTER(vp)]

@@ -663,6 +663,95 @@ class Context:
         self._ck(self.lib.bjj_elgamal_encrypt_dev(self.handle, hg, hpk, d_m, d_r, d_add_c1, d_add_c2, n, d_c1, d_c2, d_ok, stream),
                  "bjj_elgamal_encrypt_dev")
 
+    # ---- a * P + b * Q and proofs of correct decryption (include/bjj_hip_dleq.h) ----
+    def mul_pair(self, p, a, q, b, add=None):
+        """out[i] = add[i] + a[i] * p[i] + b[i] * q[i] in ONE launch (bjj_mul_pair; add=None: the identity) -> (out: (n, 64) uint8,
+        ok: (n,) uint8).  a, b: n 32-byte records (or ints) of any value, reduced mod 8l.  ok 1 = computed, 2 = p[i], q[i] or add[i] is
+        not on the curve and out[i] = (0, 0).  Byte for byte the composition of mul_var_base and point_add for on-curve points.  Not
+        constant time."""
+        pp, qq = _as_u8(p, 64, "p"), _as_u8(q, 64, "q")
+        aa, bb = _as_u8(a, 32, "a"), _as_u8(b, 32, "b")
+        n = pp.size // 64
+        ad = None if add is None else _as_u8(add, 64, "add")
+        if qq.size != n * 64 or aa.size != n * 32 or bb.size != n * 32 or (ad is not None and ad.size != n * 64):
+            raise BjjError("mul_pair: array lengths disagree")
+        out = np.empty(n * 64, dtype=np.uint8)
+        ok = np.empty(n, dtype=np.uint8)
+        self._ck(self.lib.bjj_mul_pair(self.handle, pp.ctypes.data, aa.ctypes.data, qq.ctypes.data, bb.ctypes.data,
+                                       None if ad is None else ad.ctypes.data, n, out.ctypes.data, ok.ctypes.data), "bjj_mul_pair")
+        return out.reshape(n, 64), ok
+
+    def mul_pair_dev(self, d_p, d_a, d_q, d_b, d_add, n, d_out, d_ok, stream=0):
+        """bjj_mul_pair_dev: d_p, d_q, d_out = n 64-byte records, d_a, d_b = n 32-byte records, d_add = n 64-byte records or None,
+        d_ok = n bytes, on the device"""
+        self._ck(self.lib.bjj_mul_pair_dev(self.handle, d_p, d_a, d_q, d_b, d_add, n, d_out, d_ok, stream), "bjj_mul_pair_dev")
+
+    def dleq_tag(self, g_xy, pk_xy, label=0):
+        """a transcript tag that binds G and PK: Poseidon5(G.x, G.y, PK.x, PK.y, label) through bjj_poseidon5 -> 32 bytes (uint8).
+        g_xy, pk_xy: one 64-byte point (or an (x, y) pair of ints) each; label: an int below 2^256."""
+        gg, kk = _as_u8([tuple(g_xy)] if isinstance(g_xy, (tuple, list)) else g_xy, 64, "g_xy"), \
+            _as_u8([tuple(pk_xy)] if isinstance(pk_xy, (tuple, list)) else pk_xy, 64, "pk_xy")
+        if gg.size != 64 or kk.size != 64:
+            raise BjjError("dleq_tag: one 64-byte point each for G and PK")
+        rec = np.concatenate([gg, kk, self._scalar32(label, "label")])
+        return np.ascontiguousarray(self.poseidon5(rec.reshape(1, 160))).reshape(-1).view(np.uint8)[:32].copy()
+
+    def dleq_verify(self, pk, tag, c1, d, a, b, z, g=None):
+        """ok[i] for the proof (a[i], b[i], z[i]) that log_G PK = log_c1[i] d[i] (bjj_dleq_verify): 1 = accepted, 0 = rejected (the
+        equations fail, or a proof field is not canonical), 2 = c1[i] or d[i] is not on the curve.  pk: the FixedBase of PK; g: the
+        FixedBase of G, None = B8; tag: an int or 32 bytes (dleq_tag).  Check c1 and d with in_subgroup first."""
+        hg, hpk = self._elgamal_handles(g, pk, "dleq_verify")
+        t = self._scalar32(tag, "tag")
+        cc, dd, aa, bb = _as_u8(c1, 64, "c1"), _as_u8(d, 64, "d"), _as_u8(a, 64, "a"), _as_u8(b, 64, "b")
+        zz = _as_u8(z, 32, "z")
+        n = cc.size // 64
+        if dd.size != n * 64 or aa.size != n * 64 or bb.size != n * 64 or zz.size != n * 32:
+            raise BjjError("dleq_verify: array lengths disagree")
+        ok = np.empty(n, dtype=np.uint8)
+        self._ck(self.lib.bjj_dleq_verify(self.handle, hg, hpk, t.ctypes.data, cc.ctypes.data, dd.ctypes.data, aa.ctypes.data, bb.ctypes.data,
+                                          zz.ctypes.data, n, ok.ctypes.data), "bjj_dleq_verify")
+        return ok
+
+    def dleq_verify_dev(self, pk, tag, d_c1, d_d, d_a, d_b, d_z, n, d_ok, g=None, stream=0):
+        """bjj_dleq_verify_dev: the tag on the HOST; d_c1, d_d, d_a, d_b = n 64-byte records, d_z = n 32-byte records, d_ok = n bytes,
+        on the device"""
+        hg, hpk = self._elgamal_handles(g, pk, "dleq_verify_dev")
+        t = self._scalar32(tag, "tag")
+        self._ck(self.lib.bjj_dleq_verify_dev(self.handle, hg, hpk, t.ctypes.data, d_c1, d_d, d_a, d_b, d_z, n, d_ok, stream),
+                 "bjj_dleq_verify_dev")
+
+    def _dleq_g(self, g, what):
+        if g is None:
+            return None
+        if not isinstance(g, FixedBase) or g.ctx is not self or not g.handle:
+            raise BjjError("%s: g is a live FixedBase of this context, or None for B8" % what)
+        return g.handle.value
+
+    def dleq_prove(self, sk, tag, c1, w, g=None):
+        """the partial decryptions d[i] = sk * c1[i] with their proofs (bjj_dleq_prove) -> (d, a, b: (n, 64) uint8, z: (n, 32) uint8,
+        ok: (n,) uint8).  sk, tag: an int or 32 bytes; w: n 32-byte nonces (or ints) -- fresh, uniform and secret per item; g: the
+        FixedBase of G, None = B8.  ok 1 = computed, 2 = c1[i] is not on the curve and the four outputs are zero.  Not constant time."""
+        hg = self._dleq_g(g, "dleq_prove")
+        k, t = self._scalar32(sk, "sk"), self._scalar32(tag, "tag")
+        cc, ww = _as_u8(c1, 64, "c1"), _as_u8(w, 32, "w")
+        n = cc.size // 64
+        if ww.size != n * 32:
+            raise BjjError("dleq_prove: array lengths disagree")
+        d, a, b = (np.empty(n * 64, dtype=np.uint8) for _ in range(3))
+        z = np.empty(n * 32, dtype=np.uint8)
+        ok = np.empty(n, dtype=np.uint8)
+        self._ck(self.lib.bjj_dleq_prove(self.handle, hg, k.ctypes.data, t.ctypes.data, cc.ctypes.data, ww.ctypes.data, n, d.ctypes.data,
+                                         a.ctypes.data, b.ctypes.data, z.ctypes.data, ok.ctypes.data), "bjj_dleq_prove")
+        return d.reshape(n, 64), a.reshape(n, 64), b.reshape(n, 64), z.reshape(n, 32), ok
+
+    def dleq_prove_dev(self, sk, tag, d_c1, d_w, n, d_d, d_a, d_b, d_z, d_ok, g=None, stream=0):
+        """bjj_dleq_prove_dev: sk and the tag on the HOST (read before the call returns); d_c1, d_d, d_a, d_b = n 64-byte records,
+        d_w, d_z = n 32-byte records, d_ok = n bytes, on the device"""
+        hg = self._dleq_g(g, "dleq_prove_dev")
+        k, t = self._scalar32(sk, "sk"), self._scalar32(tag, "tag")
+        self._ck(self.lib.bjj_dleq_prove_dev(self.handle, hg, k.ctypes.data, t.ctypes.data, d_c1, d_w, n, d_d, d_a, d_b, d_z, d_ok, stream),
+                 "bjj_dleq_prove_dev")
+
     def set_signer_constant_time(self, on=True):
         """signer hardening: public_keys / sign / sign_schnorr scan a small 4-bit table instead of indexing the big one
         with secret digits -- no secret-dependent address or branch; bit-identical results, ~2x slower sign"""

@@ -44,6 +44,7 @@
 #include "../../include/bjj_hip_point_sum.h"
 #include "../../include/bjj_hip_common_scalar.h"
 #include "../../include/bjj_hip_elgamal.h"
+#include "../../include/bjj_hip_dleq.h"
 #include "bjj_device.hpp"
 #include "bases.hpp"
 #include "signer.hpp"
@@ -51,6 +52,7 @@
 #include "dlog.hpp"
 #include "common_scalar.hpp"
 #include "elgamal.hpp"
+#include "dleq.hpp"
 #include "bjj_launch.hpp"
 #include "msm.hpp"
 #include "copy_pool.hpp"
@@ -264,6 +266,8 @@ struct bjj_ctx {
   int lanes_fixed_2x256 = 512;   // resident lanes per CU of K1's two-workgroup shape
   int lanes_bases = 512;         // resident lanes per CU of bjj_k_mul_bases
   int lanes_elgamal = 512;       // ... of bjj_k_elgamal_encrypt
+  int lanes_dleq = 512;          // ... of the k_dleq.hip kernels with per-lane tables (dleq_tables)
+  int occ_dleq_respond = 1;      // resident 256-lane workgroups per CU of the prover's two small kernels
   int lanes_signer = 512;        // resident lanes per CU of the bjj_k_*_verify_signer kernels
   Handles<bjj_base> user_bases;         // the tables bjj_base_create made and bjj_base_free has not released yet
   int lanes_set = 512;           // resident lanes per CU of the bjj_k_*_verify_set kernels
@@ -693,6 +697,8 @@ int bjj_init(int device, int window_bits, bjj_ctx** out_ctx) {
   c->lanes_fixed_2x256 = bjjk::fixed_base_lanes_per_cu(1);
   c->lanes_bases = bjjk::bases_lanes_per_cu();
   c->lanes_elgamal = bjjk::elgamal_lanes_per_cu();
+  c->lanes_dleq = bjjk::dleq_lanes_per_cu();
+  c->occ_dleq_respond = bjjk::occ_dleq_respond();
   c->lanes_signer = bjjk::signer_lanes_per_cu();
   c->lanes_set = bjjk::set_lanes_per_cu();
   c->dlog_launch_steps = dlog_launch_steps_from_env();
@@ -2155,6 +2161,7 @@ int bjj_schnorr_verify_set_dev(bjj_ctx* c, const bjj_signer_set* set, const void
 #include "bjj_point_sum.inc"
 #include "bjj_common_scalar.inc"
 #include "bjj_elgamal.inc"
+#include "bjj_dleq.inc"
 
 #pragma GCC visibility pop
 }  // extern "C"

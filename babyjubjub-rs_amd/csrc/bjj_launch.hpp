@@ -22,6 +22,7 @@ namespace bjj { struct SignerArgs; }  // signer.hpp: the two tables and the poin
 namespace bjj { struct SetArgs; }     // signer_set.hpp: the set's tables and keys, the B8 table (bjj_k_verify_set)
 namespace bjj { struct ElgamalArgs; } // elgamal.hpp: the three chains and the input arrays of bjj_k_elgamal_encrypt
 namespace bjj { struct CsDigits; }    // common_scalar.hpp: the recoded scalar of bjj_k_mul_common, by value in the kernel arguments
+namespace bjj { struct PairArgs; struct DleqVerifyArgs; struct DleqRespondArgs; }   // dleq.hpp: the arrays and tables of the k_dleq.hip kernels
 
 namespace bjjk {
 
@@ -206,5 +207,19 @@ hipError_t mul_common(hipStream_t st, int form, int epi, const bjj::CsDigits& D,
 int elgamal_lanes_per_cu();
 hipError_t elgamal_encrypt(hipStream_t st, int cus, int lanes_per_cu, const bjj::ElgamalArgs& A, size_t n, uint8_t* out_c1, uint8_t* out_c2,
                            uint8_t* ok, uint32_t* scratch);
+
+// k_dleq.hip: bjj_mul_pair -- out[i] = add[i] + a[i] P[i] + b[i] Q[i] (dleq.hpp; A.add may be nullptr; ok: 1, or 2 and (0, 0) for an
+// off-curve item; scratch: n * 64 bytes) -- and bjj_dleq_verify -- ok[i] = 0 / 1 / 2 --, one item per lane, 256-lane workgroups,
+// grid-strided over at most cus * lanes_per_cu lanes; vb_tables: BJJ_DLEQ_LANE_WORDS words for each of those lanes.  The prover's
+// chain starts with dleq_nonce (z[i] = w[i] mod l) and ends with dleq_respond (the hash and z; ok[i] == 1: the item has its points).
+#define BJJ_DLEQ_LANE_WORDS (2 * 36 * 9)   // two raw per-lane tables
+int dleq_lanes_per_cu();
+int dleq_block();
+int occ_dleq_respond();
+hipError_t mul_pair(hipStream_t st, int cus, int lanes_per_cu, const bjj::PairArgs& A, size_t n, uint8_t* out, uint8_t* ok, uint32_t* scratch,
+                    uint32_t* vb_tables);
+hipError_t dleq_verify(hipStream_t st, int cus, int lanes_per_cu, const bjj::DleqVerifyArgs& A, size_t n, uint8_t* ok, uint32_t* vb_tables);
+hipError_t dleq_nonce(hipStream_t st, int grid, const uint8_t* w, size_t n, uint8_t* z);
+hipError_t dleq_respond(hipStream_t st, int grid, const bjj::DleqRespondArgs& A, size_t n, const uint8_t* ok);
 
 }  // namespace bjjk
