@@ -452,3 +452,139 @@ def test_rejections(gpu_ctx, ctx_w23, statements, pair_case, proofs, prove_case)
         assert (d_out.cpu().numpy()[:n * 64].reshape(n, 64) == pair_case["out"][:n]).all()
     finally:
         foreign.close()
+
+
+# ---- overlapping launches, and the other users of the per-lane table block ---------------------------------------------------------
+def _up(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a).reshape(-1).view(np.uint8).copy()).to(torch.device("cuda", 0))
+
+
+def _zeros(sizes):
+    import torch
+    return [torch.zeros(s, dtype=torch.uint8, device=torch.device("cuda", 0)) for s in sizes]
+
+
+def _ptrs(tensors):
+    return [None if t is None else t.data_ptr() for t in tensors]
+
+
+def _same(outs, want, what):
+    for k, (o, w_) in enumerate(zip(outs, want)):
+        w_ = np.ascontiguousarray(w_).reshape(-1).view(np.uint8)
+        bad = np.nonzero(o.cpu().numpy() != w_)[0]
+        assert bad.size == 0, (what, k, bad[:8].tolist())
+
+
+def _dleq_launches(ctx, statements, pair_case, proofs, prove_case, n):
+    """name -> (enqueue(outputs, stream), output sizes in bytes, the model's arrays) for the three _dev entry points on the first n
+    items of the module's cases, the inputs uploaded once (the closures keep them alive)"""
+    d_pair = [_up(x[:n]) for x in pair_case["in"]]
+    d_c1, d_w = _up(prove_case["c1"][:n]), _up(prove_case["w"][:n])
+    out = {"pair": (lambda o, st: ctx.mul_pair_dev(*_ptrs(d_pair), n, *_ptrs(o), stream=st), [n * 64, n],
+                    [pair_case["out"][:n], pair_case["ok"][:n]])}
+    for name, s in statements.items():
+        d_v = [_up(x[:n]) for x in proofs[name]["in"]]
+        out["verify_" + name] = (lambda o, st, s=s, d_v=d_v: ctx.dleq_verify_dev(s["pk"], s["tag"], *_ptrs(d_v), n, *_ptrs(o), g=s["g"], stream=st),
+                                 [n], [proofs[name]["ok"][:n]])
+        out["prove_" + name] = (lambda o, st, s=s: ctx.dleq_prove_dev(SK, s["tag"], d_c1.data_ptr(), d_w.data_ptr(), n, *_ptrs(o), g=s["g"], stream=st),
+                                [n * 64, n * 64, n * 64, n * 32, n], [w_[:n] for w_ in prove_case["want"][name]])
+    return out
+
+
+def test_two_streams_at_once(gpu_ctx, statements, pair_case, proofs, prove_case):
+    """two launches on two streams with nothing between them, three times each pairing: bjj_mul_pair beside bjj_dleq_verify (both size
+    and index the per-lane table block of their scratch set), bjj_dleq_prove beside bjj_dleq_verify, and bjj_dleq_prove beside
+    bjj_dleq_prove with another G -- the five-launch chain on both scratch sets at once.  Every output against the model at n = NMAX"""
+    import torch
+    n = NMAX
+    L = _dleq_launches(gpu_ctx, statements, pair_case, proofs, prove_case, n)
+    streams = [torch.cuda.Stream(device=torch.device("cuda", 0)) for _ in range(2)]
+    for names in (("pair", "verify_gen13_pk5"), ("prove_b8_pk12", "verify_b8_pk12"), ("prove_b8_pk12", "prove_gen13_pk5")):
+        outs = [_zeros(L[k][1]) for k in names]
+        torch.cuda.synchronize()
+        for rep_ in range(3):
+            for k, o, st in zip(names, outs, streams):
+                L[k][0](o, st.cuda_stream)
+            gpu_ctx.sync()
+            for k, o in zip(names, outs):
+                _same(o, L[k][2], (names, k, rep_))
+                for t in o:
+                    t.zero_()
+            torch.cuda.synchronize()
+
+
+@pytest.fixture(scope="module")
+def other_users(oracle):
+    """the entry points that share the per-lane table block with the DLEQ kernels, by the C oracle: 4 097 signatures (1 in 64
+    corrupted) with their verdicts, 257 points (one off the curve) and scalars with their products"""
+    from babyjubjub_rs_amd import workload as w
+    n = 4097
+    A, R, S_, msg = w.make_signatures(oracle.mul_fixed_base, oracle.poseidon5, n)
+    bad = w.corrupt(A, R, S_, msg, n)
+    verdict = oracle.verify(A, R, S_, msg)
+    assert (verdict[~bad] == 1).all() and (verdict[bad] != 1).all() and bad[:64].any() and bad[:257].sum() >= 2
+    pts, sc = oracle.mul_fixed_base(w.scalars_254(257, offset=0x9d)).copy(), w.scalars_254(257, offset=0x5c)
+    pts[32, 7] ^= 4                                                     # off the curve: the exact kernel's item, in both sizes used
+    vb = oracle.mul_var_base(pts, sc)
+    return {"sig": [frozen(x) for x in (A, R, S_, msg)], "verdict": frozen(verdict), "pts": frozen(pts), "sc": frozen(sc), "vb": frozen(vb)}
+
+
+def _other_launches(ctx, other_users, nv, nb):
+    """(enqueue(outputs, stream), sizes, expected) for bjj_eddsa_verify_dev on nv signatures and bjj_mul_var_base_dev on nb points"""
+    u = other_users
+    d_sig = [_up(x[:nv]) for x in u["sig"]]
+    d_vb = [_up(u["pts"][:nb]), _up(u["sc"][:nb])]
+    return {"eddsa": (lambda o, st: ctx.eddsa_verify_dev(*_ptrs(d_sig), nv, *_ptrs(o), stream=st), [nv], [u["verdict"][:nv]]),
+            "var_base": (lambda o, st: ctx.mul_var_base_dev(*_ptrs(d_vb), nb, *_ptrs(o), stream=st), [nb * 64], [u["vb"][:nb]])}
+
+
+def test_back_to_back_with_the_other_users_of_the_table_block(gpu_ctx, statements, pair_case, proofs, prove_case, other_users):
+    """bjj_dleq.inc sizes the per-lane table block for cus * lanes_dleq lanes whatever n is, and says "K2 and verify use a prefix":
+    on ONE stream, with no synchronisation in between, bjj_mul_pair, bjj_eddsa_verify, bjj_dleq_verify, bjj_mul_var_base,
+    bjj_dleq_prove and bjj_mul_pair again at n = 257, each against its known result"""
+    import torch
+    n = 257
+    L = dict(_dleq_launches(gpu_ctx, statements, pair_case, proofs, prove_case, n), **_other_launches(gpu_ctx, other_users, n, n))
+    order = ("pair", "eddsa", "verify_gen13_pk5", "var_base", "prove_gen13_pk5", "pair")
+    outs = [_zeros(L[k][1]) for k in order]
+    torch.cuda.synchronize()
+    for k, o in zip(order, outs):
+        L[k][0](o, 0)
+    gpu_ctx.sync()
+    for i, (k, o) in enumerate(zip(order, outs)):
+        _same(o, L[k][2], (i, k))
+
+
+def test_first_call_of_a_fresh_context_is_dleq(statements, pair_case, proofs, other_users):
+    """the growth orders tests/test_gpu_scratch_growth.py predates DLEQ for: in a context of its own the FIRST call is bjj_mul_pair at
+    n = 1 (the table block is sized by the DLEQ rule before any other user has touched it), then bjj_eddsa_verify at 4 097,
+    bjj_dleq_verify at 64 and bjj_mul_var_base at 65, each against its known result"""
+    import torch
+    import babyjubjub_rs_amd as bjj
+    ctx = bjj.Context(0, 16)
+    try:
+        def run(launch):
+            fn, sizes, want = launch
+            o = _zeros(sizes)
+            torch.cuda.synchronize()
+            fn(o, 0)
+            ctx.sync()
+            return o, want
+
+        d_pair = [_up(x[:1]) for x in pair_case["in"]]
+        o, want = run((lambda o, st: ctx.mul_pair_dev(*_ptrs(d_pair), 1, *_ptrs(o), stream=st), [64, 1], [pair_case["out"][:1], pair_case["ok"][:1]]))
+        _same(o, want, "mul_pair at 1")
+        others = _other_launches(ctx, other_users, 4097, 65)
+        o, want = run(others["eddsa"])
+        _same(o, want, "eddsa_verify at 4097")
+        s, c = statements["b8_pk12"], proofs["b8_pk12"]                 # G = B8: the context's own table; PK's table is made here
+        pk = ctx.base(s["PK"], SETUPS["b8_pk12"][2])
+        d_v = [_up(x[:64]) for x in c["in"]]
+        o, want = run((lambda o, st: ctx.dleq_verify_dev(pk, s["tag"], *_ptrs(d_v), 64, *_ptrs(o), stream=st), [64], [c["ok"][:64]]))
+        _same(o, want, "dleq_verify at 64")
+        assert set(np.unique(c["ok"][:64])) == {0, 1, 2}
+        o, want = run(others["var_base"])
+        _same(o, want, "mul_var_base at 65")
+    finally:
+        ctx.close()
